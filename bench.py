@@ -27,6 +27,16 @@ anywhere, so a tile gather would not do). Two launch forms (plan
 --scaling weak gives every rank the full spp instead. value = pixel-samples of all ranks /
 max-over-ranks wall time. A named workload refuses to run with a product knob set in the
 environment (PRODUCT_KNOBS); every BDPT_* variable is recorded in config.env.
+
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the result
+line (headline figure, ms_per_step, the launch's kernel_ms from HIP events, config). --full adds
+what takes runs of its own: the roofline block (in-kernel counters on a separate untimed launch,
+the committed PMC traffic), the parity leg against the oracle and the CPU baselines.
+--dump-outputs DIR: rank 0 writes what the timed path returned after its last step as
+DIR/<name>.npy (float32): sample_frame (H x W x 3; under torchrun / one context the frame
+accumulated over warmup + steps, in one process with N contexts the last step's reduced frame)
+and, for the PathTracer, sample_counts (H x W). Scene, seed and sample indices are fixed by the
+arguments, so two builds run with the same arguments render the same samples.
 """
 from __future__ import annotations
 
@@ -147,6 +157,14 @@ def host_cores() -> dict:
     except (OSError, ValueError):
         pass
     return {"nproc": n, "affinity": aff, "cgroup_quota": quota, "usable": min(x for x in (n, aff, quota) if x)}
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: each array as path/<name>.npy in float32"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def progress(msg: str) -> None:
@@ -328,6 +346,64 @@ def plan_launch(gpus: int, world_size_env, devices_arg, ndev: int) -> dict:
     return {"mode": "single" if gpus == 1 else "inprocess", "world": gpus, "devices": devices}
 
 
+def roofline_block(args, B, scene, W, H, SPP, M, rr, seed, use_pt, scaling, rank, world, dev, kern_ms,
+                   named) -> dict:
+    """--full: the roofline block of the line. Algorithmic bytes of this rank's launch: in-kernel
+    counters on a separate, untimed launch of the same work (counting perturbs timing), SURVEY.md
+    §8d; the measured HBM traffic from the committed PMC passes (load_traffic)."""
+    band = [(0, H * rank // world, W, H * (rank + 1) // world - H * rank // world)]
+    if use_pt:
+        ps = B.PathTracer(scene, W, H, SPP, M, seed=seed, device=dev.index, max_tolerance=0.0,
+                          collect_stats=True)
+        ps.raytrace_tiles(band, 0, SPP)
+    else:
+        ps = B.BidirectionalPathTracer(scene, W, H, SPP, M, seed=seed, device=dev.index,
+                                       collect_stats=True, pipeline=args.pipeline, russian_roulette=rr)
+        b0, n0 = rank_sample_range(0, rank, world, SPP, scaling)
+        ps.raytrace_tiles([], b0, max(1, n0))
+    st = ps.stats()
+    ps.close()
+    bytes_launch = algorithmic_bytes(st)
+    gmem_launch = global_memory_bytes(st)
+    fetched_launch = fetched_bytes(st)
+    achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
+    traffic, traffic_info = (None, None)
+    if world == 1 and named and not use_pt and args.pipeline == 0:
+        traffic, traffic_info = load_traffic(args.workload, kern_ms)
+    roof = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
+            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5),
+            "traffic": traffic, "kernel": "k_pt" if use_pt else "k_bdpt_sample",
+            "kernel_ms": round(kern_ms, 3),
+            "algorithmic_bytes_per_launch": bytes_launch,
+            "note": "achieved / frac = SURVEY §8d algorithmic scene bytes (its convention: 32 B/child "
+                    "AABB, 36 B/triangle test, 16 B/sphere test, 40 B/closest hit; environment light: "
+                    "76 B/sampled direction, 48 B/radiance lookup, 4 B/pdf lookup) / launch time (HIP "
+                    "events on the ctx stream); fetched_* = the bytes the loads request (28 B/child of a "
+                    "4-wide node, 32 B/child of a 2-wide one, 48 B/primitive record, 48 B/shading "
+                    "record); gmem_* = the §8d bytes minus the scene reads served from the CU's LDS "
+                    "copy (the part that goes through L2 / HBM); traffic = measured HBM-side bytes "
+                    "(PMC: 2 x FETCH_SIZE + WRITE_SIZE, FETCH_SIZE counting half the bytes of every "
+                    "read width this kernel uses, tools/fetch_calib.hip; traffic_pmc.pmc_frac over the "
+                    "dispatch they were counted on)",
+            "fetched_bytes_per_launch": fetched_launch,
+            "frac_fetched_bytes": round(fetched_launch / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5),
+            "gmem_bytes_per_launch": gmem_launch,
+            "gmem_achieved": round(gmem_launch / (kern_ms * 1e-3) / 1e9, 2),
+            "gmem_frac": round(gmem_launch / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5),
+            "lds_mode": st.lds_mode,
+            "counts_per_launch": {"samples": st.samples, "node_aabbs": st.node_visits,
+                                  "node_aabbs_from_lds": st.lds_node_visits,
+                                  "tri_tests": st.tri_tests,
+                                  "sph_tests": st.sph_tests, "hits": st.hits,
+                                  "closest_rays": st.closest_rays,
+                                  "shadow_rays": st.shadow_rays,
+                                  "env_samples": st.env_samples, "env_lookups": st.env_lookups,
+                                  "env_pdf_lookups": st.env_pdf_lookups}}
+    if traffic_info:
+        roof["traffic_pmc"] = traffic_info
+    return roof
+
+
 class Timed:
     """what a timed region measured: wall seconds (max over ranks), rank 0's mean launch ms, and
     per-rank rows (elapsed s, kernel ms, pixel-samples per step, device)"""
@@ -413,6 +489,11 @@ def run_torchrun_or_single(args, B, scene, W, H, SPP, M, rr, seed, plan, use_pt,
     rows = sh.gather_floats([elapsed, kern_ms, float(rank_samples), float(gpu)])
     if args.dump_frame and rank == 0:
         np.save(args.dump_frame, frame.cpu().numpy().reshape(H, W, 3))
+    if args.dump_outputs and rank == 0:
+        arrays = {"sample_frame": frame.cpu().numpy().reshape(H, W, 3)}
+        if use_pt and world == 1:   # the counts are per context: whole only where one rank rendered every band
+            arrays["sample_counts"] = pt.read_sample_counts().reshape(H, W)
+        dump_outputs(args.dump_outputs, arrays)
     pt.close()
     t = Timed(max(r[0] for r in rows), kern_ms, rows, world)
     t.rank, t.dist, t.dev, t.t_create = rank, dist, dev, t_create
@@ -493,6 +574,11 @@ def run_inprocess(args, B, scene, W, H, SPP, M, rr, seed, plan, use_pt, scaling)
         samples = [W * H * B.rank_sample_range(0, r, N, SPP, scaling)[1] for r in range(N)]
     if args.dump_frame:
         np.save(args.dump_frame, pts[0].read_frame(B.FRAME_SAMPLE))
+    if args.dump_outputs:
+        arrays = {"sample_frame": pts[0].read_frame(B.FRAME_SAMPLE).reshape(H, W, 3)}
+        if use_pt:   # context 0 holds the reduced counts
+            arrays["sample_counts"] = pts[0].read_sample_counts().reshape(H, W)
+        dump_outputs(args.dump_outputs, arrays)
     rccl_ranks = red.ranks
     red.close()
     for p in pts:
@@ -526,8 +612,14 @@ def main() -> int:
                          "torchrun, 0..N-1 in one process), e.g. 0,0")
     ap.add_argument("--dump-frame", default=None,
                     help="rank 0 saves the last step's reduced sample frame (.npy, H x W x 3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the timed path returned after its last step as DIR/<name>.npy "
+                         "(float32): sample_frame, and sample_counts for --integrator pt")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline block (counters on a separate untimed launch, PMC traffic), the "
+                         "parity leg against the oracle and the CPU baselines; a plain run only times the steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity leg")
     ap.add_argument("--scene", default=None, help="override: a .dae path")
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
@@ -543,6 +635,8 @@ def main() -> int:
                          "unidirectional PathTracer, DESIGN.md §10; adaptive sampling off: every "
                          "pixel takes all spp; ranks split the frame into row bands)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"bench.py: --steps {args.steps} --warmup {args.warmup}: need steps >= 1, warmup >= 0")
     wl = WORKLOADS[args.workload]
     scene_path = args.scene or os.path.join(REPO, wl[0])
     W = args.width or wl[1]
@@ -588,28 +682,11 @@ def main() -> int:
     kern_ms, elapsed = t.kern_ms, t.elapsed
     samples_per_step = t.samples_per_step
 
-    # algorithmic bytes of rank 0's launch: in-kernel counters on a separate, untimed launch of
-    # the same work (counting perturbs timing), SURVEY.md §8d.
-    band = [(0, H * rank // world, W, H * (rank + 1) // world - H * rank // world)]
-    if use_pt:
-        ps = B.PathTracer(scene, W, H, SPP, M, seed=seed, device=dev.index, max_tolerance=0.0,
-                          collect_stats=True)
-        ps.raytrace_tiles(band, 0, SPP)
-    else:
-        ps = B.BidirectionalPathTracer(scene, W, H, SPP, M, seed=seed, device=dev.index,
-                                       collect_stats=True, pipeline=args.pipeline, russian_roulette=rr)
-        b0, n0 = rank_sample_range(0, rank, world, SPP, scaling)
-        ps.raytrace_tiles([], b0, max(1, n0))
-    st = ps.stats()
-    ps.close()
-    bytes_launch = algorithmic_bytes(st)
-    gmem_launch = global_memory_bytes(st)
-    fetched_launch = fetched_bytes(st)
-    achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
     value = samples_per_step * args.steps / elapsed / 1e6
-    traffic, traffic_info = (None, None)
-    if world == 1 and named and not use_pt and args.pipeline == 0:
-        traffic, traffic_info = load_traffic(args.workload, kern_ms)
+    roofline = None
+    if args.full:   # every rank takes its own counted launch; rank 0's goes into the line
+        roofline = roofline_block(args, B, scene, W, H, SPP, M, rr, seed, use_pt, scaling, rank, world, dev,
+                                  kern_ms, named)
 
     if rank != 0:
         if dist is not None:
@@ -646,38 +723,11 @@ def main() -> int:
                    "launch": plan["mode"],
                    "env": knobs,
                    "host_setup_s": {"dae_load": round(t_load, 3), "bdpt_create": round(t.t_create, 3)}},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5),
-                     "traffic": traffic, "kernel": "k_pt" if use_pt else "k_bdpt_sample",
-                     "kernel_ms": round(kern_ms, 3),
-                     "algorithmic_bytes_per_launch": bytes_launch,
-                     "note": "achieved / frac = SURVEY §8d algorithmic scene bytes (its convention: 32 B/child "
-                             "AABB, 36 B/triangle test, 16 B/sphere test, 40 B/closest hit; environment light: "
-                             "76 B/sampled direction, 48 B/radiance lookup, 4 B/pdf lookup) / launch time (HIP "
-                             "events on the ctx stream); fetched_* = the bytes the loads request (28 B/child of a "
-                             "4-wide node, 32 B/child of a 2-wide one, 48 B/primitive record, 48 B/shading "
-                             "record); gmem_* = the §8d bytes minus the scene reads served from the CU's LDS "
-                             "copy (the part that goes through L2 / HBM); traffic = measured HBM-side bytes "
-                             "(PMC: 2 x FETCH_SIZE + WRITE_SIZE, FETCH_SIZE counting half the bytes of every "
-                             "read width this kernel uses, tools/fetch_calib.hip; traffic_pmc.pmc_frac over the "
-                             "dispatch they were counted on)",
-                     "fetched_bytes_per_launch": fetched_launch,
-                     "frac_fetched_bytes": round(fetched_launch / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5),
-                     "gmem_bytes_per_launch": gmem_launch,
-                     "gmem_achieved": round(gmem_launch / (kern_ms * 1e-3) / 1e9, 2),
-                     "gmem_frac": round(gmem_launch / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5),
-                     "lds_mode": st.lds_mode,
-                     "counts_per_launch": {"samples": st.samples, "node_aabbs": st.node_visits,
-                                           "node_aabbs_from_lds": st.lds_node_visits,
-                                           "tri_tests": st.tri_tests,
-                                           "sph_tests": st.sph_tests, "hits": st.hits,
-                                           "closest_rays": st.closest_rays,
-                                           "shadow_rays": st.shadow_rays,
-                                           "env_samples": st.env_samples, "env_lookups": st.env_lookups,
-                                           "env_pdf_lookups": st.env_pdf_lookups}},
+        "kernel_ms": round(kern_ms, 3),
+        "full": args.full,
     }
-    if traffic_info:
-        out["roofline"]["traffic_pmc"] = traffic_info
+    if roofline is not None:
+        out["roofline"] = roofline
     if t.rccl_ranks is not None:
         out["rccl_ranks"] = t.rccl_ranks
     if world > 1 or dist is not None:
@@ -687,13 +737,13 @@ def main() -> int:
                            "backend": t.backend}
     if use_pt:
         out["config"]["integrator"] = "PathTracer (pathtracer.cpp:47-340)"
-    cores = host_cores()
-    thr = cores["usable"]
     progress(f"timed {args.steps} steps: {value:.1f} Msamples/s")
-    if world == 1 and not args.no_parity and not use_pt:
+    cores = host_cores() if args.full else None
+    thr = cores["usable"] if args.full else None
+    if args.full and world == 1 and not args.no_parity and not use_pt:
         progress("parity leg: GPU vs oracle modes 2 and 1")
         out["parity"] = parity_check(scene, W, H, M, seed, rr=rr, threads=thr)
-    if world == 1 and not args.no_cpu_baseline and not use_pt:
+    if args.full and world == 1 and not args.no_cpu_baseline and not use_pt:
         progress("CPU baseline: oracle port")
         port = cpu_baseline(scene, os.path.basename(scene_path), W, H, SPP, M, threads=thr, rr=rr)
         # the reference cannot run the environment light / roulette under BDPT: port only

@@ -3,13 +3,13 @@
 #   PART=tests    the whole `pytest -m gpu` suite
 #   PART=phases   phase split + lane use per phase (BDPT_PHASE_PROF variants build_var_ph.so (m <= 5)
 #                 and build_var_ph8.so (m <= 8), tools/build_variants.sh) on the north star and C5
-#   PART=bench    bench.py on WORKLOADS (default: ns c2 c3 c4 c5); ROCPROF=1 adds the rocprofv3
+#   PART=bench    bench.py --full on WORKLOADS (default: ns c2 c3 c4 c5); ROCPROF=1 adds the rocprofv3
 #                 kernel stats of the default line
 #   PART=pmc      FETCH_SIZE / WRITE_SIZE passes per workload -> traffic_<w>.json, SQ / TCC groups
 #                 for WORKLOADS_SQ (default ns c5)
 #   PART=ab       A/B of variant libraries: LIBS="build_var_a.so build_var_b.so ..." on CFGS
 #                 (prof_render.py argument strings separated by ';'), ROUNDS interleaved rounds
-#   PART=pt       bench.py --integrator pt (the PathTracer) on ns, c2, a microfacet scene, bunny.dae
+#   PART=pt       bench.py --full --integrator pt (the PathTracer) on ns, c2, a microfacet scene, bunny.dae
 #   PART=full     tests, then bench
 # Every GPU step runs under its own timeout; the script stops at the first abort / fault / timeout.
 cd "$(dirname "$0")/.." || exit 1
@@ -89,10 +89,10 @@ if [ "$PART" = pmc ]; then
 fi
 if [ "$PART" = pt ]; then
   # the unidirectional PathTracer on the BDPT workloads' scenes and the ones only it renders
-  step bench_pt_ns 600 python bench.py --integrator pt --workload ns --steps 3 --warmup 1 --no-cpu-baseline
-  step bench_pt_c2 600 python bench.py --integrator pt --workload c2 --steps 3 --warmup 1 --no-cpu-baseline
-  step bench_pt_mf 600 python bench.py --integrator pt --scene scenes/CBspheres_microfacet_al_ag.dae --steps 3 --warmup 1 --no-cpu-baseline
-  step bench_pt_bunny 600 python bench.py --integrator pt --scene scenes/bunny.dae --steps 3 --warmup 1 --no-cpu-baseline
+  step bench_pt_ns 600 python bench.py --integrator pt --workload ns --steps 3 --warmup 1 --full --no-cpu-baseline
+  step bench_pt_c2 600 python bench.py --integrator pt --workload c2 --steps 3 --warmup 1 --full --no-cpu-baseline
+  step bench_pt_mf 600 python bench.py --integrator pt --scene scenes/CBspheres_microfacet_al_ag.dae --steps 3 --warmup 1 --full --no-cpu-baseline
+  step bench_pt_bunny 600 python bench.py --integrator pt --scene scenes/bunny.dae --steps 3 --warmup 1 --full --no-cpu-baseline
   if [ -n "$ROCPROF" ]; then
     step rocprof_pt 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_pt -o run -- python3 bench.py --integrator pt --steps 3 --warmup 1 --no-cpu-baseline --no-parity
   fi
@@ -101,7 +101,7 @@ if [ "$PART" = bench ] || [ "$PART" = full ]; then
   for w in ${WORKLOADS:-ns c2 c3 c4 c5}; do
     extra=""; [ "$w" != ns ] && extra="--no-cpu-baseline"
     [ "$w" = c4 ] || [ "$w" = c5 ] && extra="$extra --steps 2"
-    step bench_$w 900 python bench.py --workload $w $extra
+    step bench_$w 900 python bench.py --full --workload $w $extra
   done
   if [ -n "$ROCPROF" ]; then
     step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity
