@@ -187,33 +187,39 @@ constexpr int kMaxDepth = 126;   // the deepest k_bdpt_sample instantiation (MAX
 #define PH_STAMP(v)
 #endif
 
-// Stages the block's LDS copy of the scene (LM 1: whole tree + geometry; LM 2: the BFS treelet;
-// LM 3: the flat leaf list with its geometry and shading records) behind the wave queues, and the
-// materials / lights, and points kp.S at them.
+// Stages the block's LDS copy of the scene at sc (LM 1: whole tree + geometry; LM 2: the BFS
+// treelet; LM 3: the flat leaf list with its geometry and shading records) and points S at it.
+template <int LM>
+__device__ __forceinline__ void stage_lds_scene(SceneView& S, int n_node4, int n_geom4, float4* sc) {
+  if (LM != 0) {
+    const int nn = LM == 1 ? n_node4 : LM == 3 ? 0 : node_f4(lm_width(LM)) * S.ntop;
+    const int n4 = nn + (LM == 1 || LM == 3 ? n_geom4 : 0);
+    for (int k = threadIdx.x; k < n4; k += blockDim.x)
+      sc[k] = k < nn ? S.nodes[k] : S.geom[k - nn];
+    if (LM == 3) {
+      int* lv = (int*)(sc + n4);
+      for (int k = threadIdx.x; k < S.nleaves; k += blockDim.x) lv[k] = S.lleaves[k];
+      S.lleaves = lv;
+      float4* ls = sc + n4 + (S.nleaves + 3) / 4;   // shading records after the leaf list
+      for (int k = threadIdx.x; k < n_geom4; k += blockDim.x) ls[k] = S.shade[k];
+      S.lshade = ls;
+    }
+    __syncthreads();
+    S.lnodes = sc;
+    S.lgeom = sc + nn;
+  }
+}
+
+// k_bdpt_sample's LDS: the scene copy behind the wave queues and the traversal stacks' overflow
+// slots, and the materials / lights; points kp.S at them.
 template <int LM>
 __device__ __forceinline__ void stage_scene(KParams& kp, unsigned char* smem, DMat* s_mats, DLight* s_lights) {
   static_assert(kLdsStackStride == kBlock, "LDS stack stride = lanes per block");
   const bool lst = (LM == 1 || LM == 2) && kLdsStack > 0 && kp.lstack_on;
   if (lst)   // the traversal stacks' LDS overflow slots, behind the wave queues
     kp.S.lstack = (int*)(smem + kWavesPerBlock * sizeof(WaveQ));
-  if (LM != 0) {
-    float4* sc = (float4*)(smem + kWavesPerBlock * sizeof(WaveQ) + (lst ? kLdsStackBytes : 0));
-    const int nn = LM == 1 ? kp.n_node4 : LM == 3 ? 0 : node_f4(lm_width(LM)) * kp.S.ntop;
-    const int n4 = nn + (LM == 1 || LM == 3 ? kp.n_geom4 : 0);
-    for (int k = threadIdx.x; k < n4; k += blockDim.x)
-      sc[k] = k < nn ? kp.S.nodes[k] : kp.S.geom[k - nn];
-    if (LM == 3) {
-      int* lv = (int*)(sc + n4);
-      for (int k = threadIdx.x; k < kp.S.nleaves; k += blockDim.x) lv[k] = kp.S.lleaves[k];
-      kp.S.lleaves = lv;
-      float4* ls = sc + n4 + (kp.S.nleaves + 3) / 4;   // shading records after the leaf list
-      for (int k = threadIdx.x; k < kp.n_geom4; k += blockDim.x) ls[k] = kp.S.shade[k];
-      kp.S.lshade = ls;
-    }
-    __syncthreads();
-    kp.S.lnodes = sc;
-    kp.S.lgeom = sc + nn;
-  }
+  stage_lds_scene<LM>(kp.S, kp.n_node4, kp.n_geom4,
+                      (float4*)(smem + kWavesPerBlock * sizeof(WaveQ) + (lst ? kLdsStackBytes : 0)));
   if (kp.nmat <= kLdsMats && kp.S.nlights <= kLdsLights) {
     for (int k = threadIdx.x; k < kp.nmat; k += blockDim.x) s_mats[k] = kp.S.mats[k];
     for (int k = threadIdx.x; k < kp.S.nlights; k += blockDim.x) s_lights[k] = kp.S.lights[k];
@@ -234,6 +240,26 @@ struct Item {
   int x, y, s0, my_n;   // this lane's pixel and sample range [s0, s0 + my_n)
   unsigned idx;         // item index relative to kp.item_lo
 };
+// Pixel block blk (<= 8x8: an entry of the tile block list, or a cell of the full frame's grid) and
+// the lane's pixel in it; false (and pixel 0, 0) for a lane outside the block.
+__device__ __forceinline__ bool block_pixel(const int4* blocks, int nbx, int W, int H, int blk, int lane, int& x,
+                                            int& y) {
+  int bx0, by0, bw, bh;
+  if (blocks) {
+    int4 bb = blocks[blk];
+    bx0 = bb.x; by0 = bb.y; bw = bb.z; bh = bb.w;
+  } else {
+    bx0 = (blk % nbx) * 8;
+    by0 = (blk / nbx) * 8;
+    bw = min(8, W - bx0);
+    bh = min(8, H - by0);
+  }
+  const int qx = lane & 7, qy = lane >> 3;
+  const bool in = qx < bw && qy < bh;
+  x = in ? bx0 + qx : 0;
+  y = in ? by0 + qy : 0;
+  return in;
+}
 __device__ __forceinline__ bool next_item(const KParams& kp, int lane, int grp, int& cur, Item& it) {
   unsigned item = 0;
   if (kp.xcd) {
@@ -265,22 +291,8 @@ __device__ __forceinline__ bool next_item(const KParams& kp, int lane, int grp, 
     chunk = (int)(item / (unsigned)kp.nblocks);
     blk = (int)(item - (unsigned)chunk * (unsigned)kp.nblocks);
   }
-  int bx0, by0, bw, bh;
-  if (kp.blocks) {
-    int4 bb = kp.blocks[blk];
-    bx0 = bb.x; by0 = bb.y; bw = bb.z; bh = bb.w;
-  } else {
-    bx0 = (blk % kp.nbx) * 8;
-    by0 = (blk / kp.nbx) * 8;
-    bw = min(8, kp.sp.W - bx0);
-    bh = min(8, kp.sp.H - by0);
-  }
-  const int qx = lane & 7, qy = lane >> 3;
-  it.x = 0; it.y = 0;
   int s0 = 0, s1 = 0;
-  if (qx < bw && qy < bh) {
-    it.x = bx0 + qx;
-    it.y = by0 + qy;
+  if (block_pixel(kp.blocks, kp.nbx, kp.sp.W, kp.sp.H, blk, lane, it.x, it.y)) {
     s0 = kp.spp_begin + chunk * kp.spl;
     s1 = min(s0 + kp.spl, kp.spp_end);
   }
@@ -418,16 +430,18 @@ __device__ __forceinline__ void finish_item(const KParams& kp, WaveQ& q, const I
   __builtin_amdgcn_wave_barrier();
 }
 
-template <bool STATS>
-__device__ __forceinline__ void flush_stats(const KParams& kp, int lane, unsigned nsamp, const Counters& cnt) {
+// The wave's counters added to the context's statistics; N: how many of them the kernel keeps (8:
+// the scene counters, k_pt; 11: with the environment-table reads, k_bdpt_sample).
+template <bool STATS, int N>
+__device__ __forceinline__ void flush_stats(unsigned long long* stats, int lane, unsigned nsamp, const Counters& cnt) {
   if (STATS) {
     // slots 0..7 the scene counters, 12..14 the environment-table reads (15: tickets, 16..31: phase profile)
     unsigned v[11] = {nsamp, cnt.closest, cnt.shadow, cnt.nodes, cnt.tris, cnt.sphs, cnt.hits, cnt.lnodes,
                       cnt.env_s, cnt.env_l, cnt.env_p};
 #pragma unroll
-    for (int k = 0; k < 11; k++) {
+    for (int k = 0; k < N; k++) {
       unsigned s = wave_sum(v[k]);
-      if (lane == 0 && s) atomicAdd(kp.stats + (k < 8 ? k : k + 4), (unsigned long long)s);
+      if (lane == 0 && s) atomicAdd(stats + (k < 8 ? k : k + 4), (unsigned long long)s);
     }
   }
 }
@@ -524,7 +538,7 @@ __global__ __launch_bounds__(kBlock, kMinWaves) void k_bdpt_sample(KParams kp) {
     }
   }
 #endif
-  flush_stats<STATS>(kp, lane, nsamp, cnt);
+  flush_stats<STATS, 11>(kp.stats, lane, nsamp, cnt);
 }
 
 // k_pt: the unidirectional PathTracer (bdpt_core.h pt_pixel). Persistent waves take 8x8 pixel
@@ -546,23 +560,7 @@ template <bool STATS, int LM>
 __global__ __launch_bounds__(kBlock, kMinWaves) void k_pt(PtKParams kp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
-  if (LM != 0) {
-    float4* sc = (float4*)smem;
-    const int nn = LM == 1 ? kp.n_node4 : LM == 3 ? 0 : node_f4(lm_width(LM)) * kp.S.ntop;
-    const int n4 = nn + (LM == 1 || LM == 3 ? kp.n_geom4 : 0);
-    for (int k = threadIdx.x; k < n4; k += blockDim.x) sc[k] = k < nn ? kp.S.nodes[k] : kp.S.geom[k - nn];
-    if (LM == 3) {
-      int* lv = (int*)(sc + n4);
-      for (int k = threadIdx.x; k < kp.S.nleaves; k += blockDim.x) lv[k] = kp.S.lleaves[k];
-      kp.S.lleaves = lv;
-      float4* ls = sc + n4 + (kp.S.nleaves + 3) / 4;   // shading records after the leaf list
-      for (int k = threadIdx.x; k < kp.n_geom4; k += blockDim.x) ls[k] = kp.S.shade[k];
-      kp.S.lshade = ls;
-    }
-    __syncthreads();
-    kp.S.lnodes = sc;
-    kp.S.lgeom = sc + nn;
-  }
+  stage_lds_scene<LM>(kp.S, kp.n_node4, kp.n_geom4, (float4*)smem);   // no stack slots, no material / light copy
   Counters cnt = {0, 0, 0, 0, 0, 0};
   unsigned nsamp = 0;
   for (;;) {
@@ -570,19 +568,8 @@ __global__ __launch_bounds__(kBlock, kMinWaves) void k_pt(PtKParams kp) {
     if (lane == 0) item = atomicAdd(kp.work, 1u);
     item = __shfl(item, 0, 64);
     if (item >= (unsigned)kp.nblocks) break;
-    int bx0, by0, bw, bh;
-    if (kp.blocks) {
-      const int4 bb = kp.blocks[item];
-      bx0 = bb.x; by0 = bb.y; bw = bb.z; bh = bb.w;
-    } else {
-      bx0 = ((int)item % kp.nbx) * 8;
-      by0 = ((int)item / kp.nbx) * 8;
-      bw = min(8, kp.pp.W - bx0);
-      bh = min(8, kp.pp.H - by0);
-    }
-    const int qx = lane & 7, qy = lane >> 3;
-    if (qx < bw && qy < bh) {
-      const int x = bx0 + qx, y = by0 + qy;
+    int x, y;
+    if (block_pixel(kp.blocks, kp.nbx, kp.pp.W, kp.pp.H, (int)item, lane, x, y)) {
       int n = 0;
       const f3 v = pt_pixel<LM>(kp.S, kp.pp, cnt, x, y, &n);
       const size_t k = (size_t)x + (size_t)y * kp.pp.W;
@@ -593,14 +580,7 @@ __global__ __launch_bounds__(kBlock, kMinWaves) void k_pt(PtKParams kp) {
       nsamp += (unsigned)n;
     }
   }
-  if (STATS) {
-    unsigned v[8] = {nsamp, cnt.closest, cnt.shadow, cnt.nodes, cnt.tris, cnt.sphs, cnt.hits, cnt.lnodes};
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      unsigned s = wave_sum(v[k]);
-      if (lane == 0 && s) atomicAdd(kp.stats + k, (unsigned long long)s);
-    }
-  }
+  flush_stats<STATS, 8>(kp.stats, lane, nsamp, cnt);
 }
 
 __global__ void k_trace_rays(SceneView S, const float* rays, int n, int any_hit, float* out_t, int* out_prim,
@@ -640,42 +620,55 @@ static_assert(kLdsSceneMax > kLdsStackBytes + (size_t)node_bytes(lm_width(2)), "
 
 // Persistent launch: as many blocks as are co-resident (occupancy query with this launch's LDS),
 // never more waves than work items.
-template <class K>
-int launch_persistent(Ctx* c, K kernel, size_t lds, const KParams& kp) {
+template <class K, class KP>
+int launch_persistent(Ctx* c, K kernel, const char* name, size_t lds, const KP& kp, long long items) {
   int per_cu = 0;
   HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, lds));
-  if (per_cu <= 0) { g_err = "k_bdpt_sample cannot be resident (LDS/VGPR budget)"; return BDPT_E_DEVICE; }
-  long long grid = std::min<long long>((long long)per_cu * c->ncu,
-                                       ((long long)kp.nitems + kWavesPerBlock - 1) / kWavesPerBlock);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kBlock), lds, c->stream, kp);
+  if (per_cu <= 0) { g_err = std::string(name) + " cannot be resident (LDS/VGPR budget)"; return BDPT_E_DEVICE; }
+  long long grid = std::min<long long>((long long)per_cu * c->ncu, (items + kWavesPerBlock - 1) / kWavesPerBlock);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)std::max(1LL, grid)), dim3(kBlock), lds, c->stream, kp);
   HIPCHK(hipGetLastError());
   return BDPT_OK;
 }
 
-// The LDS mode of a BDPT launch and the dynamic LDS it needs (wave queues + the scene copy).
-int pick_lm(Ctx* c, KParams& kp, size_t* lds) {
-  const size_t q = kWavesPerBlock * sizeof(WaveQ);
-  const size_t full = (c->hs.tree(lm_width(1)).nodes.size() + c->hs.geom.size()) * sizeof(float);
+// The block's LDS copy of the scene for a kernel with lds_max bytes for it: the LDS mode
+// (BDPT_LDS_MODE's, else the flat list for tiny scenes, else the whole scene, else the treelet; a
+// mode that does not fit or has nothing to stage falls back 3 -> 1 -> 2 -> 0), the view and node
+// count of that mode, and the bytes of the flat and whole-scene copies. treelet_max: the bytes a
+// treelet may take. Returns the mode.
+template <class KP>
+int pick_lds_copy(Ctx* c, KP& kp, size_t lds_max, size_t treelet_max, size_t* flat, size_t* full) {
+  *full = (c->hs.tree(lm_width(1)).nodes.size() + c->hs.geom.size()) * sizeof(float);
   const bool has_nodes = !c->hs.bvh2.nodes.empty();
   // LM 3's LDS: geometry, leaf list (padded to 16 B), shading records
-  const size_t flat = 2 * c->hs.geom.size() * sizeof(float) + (c->hs.leaf_refs.size() + 3) / 4 * 16;
+  *flat = 2 * c->hs.geom.size() * sizeof(float) + (c->hs.leaf_refs.size() + 3) / 4 * 16;
   int lm = c->env_lds_mode >= 0 ? c->env_lds_mode   // diagnostics: BDPT_LDS_MODE forces 0 / 1 / 2 / 3
-               : (c->hs.nprim <= kFlatMaxPrims && flat <= kLdsSceneMax) ? 3
-               : (full <= kLdsSceneMax ? 1 : has_nodes ? 2 : 0);
-  if (lm == 3 && flat > kLdsSceneMax) lm = 1;
-  if (lm == 1 && full > kLdsSceneMax) lm = 2;
+               : (c->hs.nprim <= kFlatMaxPrims && *flat <= lds_max) ? 3
+               : (*full <= lds_max ? 1 : has_nodes ? 2 : 0);
+  if (lm == 3 && *flat > lds_max) lm = 1;
+  if (lm == 1 && *full > lds_max) lm = 2;
   if (lm == 2 && !has_nodes) lm = 0;
   kp.S = view_of(c, lm);
   kp.n_node4 = (int)(c->hs.tree(lm_width(lm)).nodes.size() / 4);
   if (lm == 2) kp.S.ntop = (int)std::min<size_t>((size_t)c->hs.tree(lm_width(2)).n_top,
-                                                 (kLdsSceneMax - kLdsStackBytes) / node_bytes(lm_width(2)));
-  if (lm == 2 && c->env_ntop_max >= 0) kp.S.ntop = std::min(kp.S.ntop, c->env_ntop_max);   // diagnostics
+                                                 treelet_max / node_bytes(lm_width(2)));
   c->last_lm = lm;
+  return lm;
+}
+// the bytes of mode lm's copy
+size_t lds_copy_bytes(int lm, const SceneView& S, size_t flat, size_t full) {
+  return lm == 3 ? flat : lm == 1 ? full : lm == 2 ? (size_t)S.ntop * node_bytes(lm_width(2)) : 0;
+}
+
+// The LDS mode of a BDPT launch and the dynamic LDS it needs (wave queues + the scene copy).
+int pick_lm(Ctx* c, KParams& kp, size_t* lds) {
+  size_t flat, full;
+  const int lm = pick_lds_copy(c, kp, kLdsSceneMax, kLdsSceneMax - kLdsStackBytes, &flat, &full);
+  if (lm == 2 && c->env_ntop_max >= 0) kp.S.ntop = std::min(kp.S.ntop, c->env_ntop_max);   // diagnostics
   // LM 2 always gives the stacks their LDS slots (the treelet makes room); LM 1 when the whole
   // scene and the slots fit together (CBgems: +0.5 .. +0.8 %, profiles/r04o_ab_stack_lm1.log)
   kp.lstack_on = lm == 2 || (lm == 1 && full + kLdsStackBytes <= kLdsSceneMax);
-  *lds = q + (kp.lstack_on ? kLdsStackBytes : 0) +
-         (lm == 3 ? flat : lm == 1 ? full : lm == 2 ? (size_t)kp.S.ntop * node_bytes(lm_width(2)) : 0);
+  *lds = kWavesPerBlock * sizeof(WaveQ) + (kp.lstack_on ? kLdsStackBytes : 0) + lds_copy_bytes(lm, kp.S, flat, full);
   return lm;
 }
 
@@ -683,10 +676,10 @@ template <int MAXV, bool STATS, bool EXT>
 int launch_lm(Ctx* c, KParams& kp) {
   size_t lds = 0;
   const int lm = pick_lm(c, kp, &lds);
-  if (lm == 3) return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 3, EXT>, lds, kp);
-  if (lm == 1) return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 1, EXT>, lds, kp);
-  if (lm == 2) return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 2, EXT>, lds, kp);
-  return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 0, EXT>, lds, kp);
+  if (lm == 3) return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 3, EXT>, "k_bdpt_sample", lds, kp, kp.nitems);
+  if (lm == 1) return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 1, EXT>, "k_bdpt_sample", lds, kp, kp.nitems);
+  if (lm == 2) return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 2, EXT>, "k_bdpt_sample", lds, kp, kp.nitems);
+  return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 0, EXT>, "k_bdpt_sample", lds, kp, kp.nitems);
 }
 
 template <int MAXV>
@@ -695,36 +688,17 @@ int launch_maxv(Ctx* c, KParams& kp) {
   return c->prm.collect_stats ? launch_lm<MAXV, true, false>(c, kp) : launch_lm<MAXV, false, false>(c, kp);
 }
 
-template <class K, class KP>
-int launch_persistent_pt(Ctx* c, K kernel, size_t lds, const KP& kp, long long items) {
-  int per_cu = 0;
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, lds));
-  if (per_cu <= 0) { g_err = "k_pt cannot be resident (LDS/VGPR budget)"; return BDPT_E_DEVICE; }
-  long long grid = std::min<long long>((long long)per_cu * c->ncu, (items + kWavesPerBlock - 1) / kWavesPerBlock);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)std::max(1LL, grid)), dim3(kBlock), lds, c->stream, kp);
-  HIPCHK(hipGetLastError());
-  return BDPT_OK;
-}
-
 template <bool STATS>
 int launch_pt(Ctx* c, PtKParams& kp) {
-  const size_t full = (c->hs.tree(lm_width(1)).nodes.size() + c->hs.geom.size()) * sizeof(float);
-  const size_t lds_max = kLdsPerCu / kBlocksPerCu - 256;
-  // LM 3's LDS: geometry, leaf list (padded to 16 B), shading records
-  const size_t flat = 2 * c->hs.geom.size() * sizeof(float) + (c->hs.leaf_refs.size() + 3) / 4 * 16;
-  int lm = c->env_lds_mode >= 0 ? c->env_lds_mode
-               : (c->hs.nprim <= kFlatMaxPrims && flat <= lds_max) ? 3 : (full <= lds_max ? 1 : 2);
-  if (lm == 3 && flat > lds_max) lm = 1;
-  if (lm == 1 && full > lds_max) lm = 2;
-  c->last_lm = lm;
-  kp.S = view_of(c, lm);
-  kp.n_node4 = (int)(c->hs.tree(lm_width(lm)).nodes.size() / 4);
+  const size_t lds_max = kLdsPerCu / kBlocksPerCu - 256;   // k_pt's LDS holds the scene copy only
+  size_t flat, full;
+  const int lm = pick_lds_copy(c, kp, lds_max, lds_max, &flat, &full);
   kp.n_geom4 = (int)(c->hs.geom.size() / 4);
-  if (lm == 2) kp.S.ntop = (int)std::min<size_t>((size_t)c->hs.tree(lm_width(2)).n_top, lds_max / node_bytes(lm_width(2)));
-  if (lm == 3) return launch_persistent_pt(c, k_pt<STATS, 3>, flat, kp, kp.nblocks);
-  if (lm == 1) return launch_persistent_pt(c, k_pt<STATS, 1>, full, kp, kp.nblocks);
-  if (lm == 2) return launch_persistent_pt(c, k_pt<STATS, 2>, (size_t)kp.S.ntop * node_bytes(lm_width(2)), kp, kp.nblocks);
-  return launch_persistent_pt(c, k_pt<STATS, 0>, 0, kp, kp.nblocks);
+  const size_t lds = lds_copy_bytes(lm, kp.S, flat, full);
+  if (lm == 3) return launch_persistent(c, k_pt<STATS, 3>, "k_pt", lds, kp, kp.nblocks);
+  if (lm == 1) return launch_persistent(c, k_pt<STATS, 1>, "k_pt", lds, kp, kp.nblocks);
+  if (lm == 2) return launch_persistent(c, k_pt<STATS, 2>, "k_pt", lds, kp, kp.nblocks);
+  return launch_persistent(c, k_pt<STATS, 0>, "k_pt", lds, kp, kp.nblocks);
 }
 
 void free_ctx(Ctx* c) {

@@ -2,9 +2,10 @@
 """Static code statistics of the megakernel instantiations (no GPU needed).
 
 Compiles bidirectional-pathtracing_amd/csrc/bdpt_hip.hip for gfx950 to assembly with the product
-flags (plus any extra -D flags given on the command line) and prints, per k_bdpt_sample
-instantiation: VGPRs, scratch bytes per lane, code size, instruction count, scratch / VMEM / LDS
-instruction counts and exec-mask bookkeeping. Used to pre-screen A/B variants before a GPU run.
+flags (plus any extra -D flags given on the command line) and prints, per k_bdpt_sample and k_pt
+instantiation (the STATS = false ones): VGPRs, scratch bytes per lane, code size, instruction
+count, scratch / VMEM / LDS instruction counts and exec-mask bookkeeping. Used to pre-screen A/B
+variants before a GPU run.
 
   python3 tools/asm_stats.py [-DFOO=1 ...]     (ASM_EXTRA="-mllvm ..." adds other compiler flags)
 """
@@ -28,12 +29,14 @@ cmd = [ge.HIPCC] + [f for f in ge.HIP_FLAGS if f not in ("-fPIC",)] + [
     os.path.join(CS, "bdpt_hip.hip"), "-o", out] + extra
 subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
 s = open(out).read().split("\n")
-want = re.compile(r"^(_ZN12_GLOBAL__N_113k_bdpt_sampleILi(\d+)ELb0ELi(\d)ELb(\d)EEEvNS_7KParamsE):")
+want = re.compile(r"^_ZN12_GLOBAL__N_1(?:13k_bdpt_sampleILi(\d+)ELb0ELi(\d)ELb(\d)EEEvNS_7KParamsE|"
+                  r"4k_ptILb0ELi(\d)EEEvNS_9PtKParamsE):")
 for i, line in enumerate(s):
     m = want.match(line)
     if not m:
         continue
-    name, maxv, lm, ext = m.groups()
+    maxv, lm, ext, pt_lm = m.groups()
+    label = f"k_pt LM={pt_lm}" if pt_lm else f"MAXV={maxv} LM={lm} EXT={ext}"
     j = i
     while not s[j].startswith(".Lfunc_end"):
         j += 1
@@ -51,6 +54,6 @@ for i, line in enumerate(s):
     vm = sum(v for k, v in c.items() if k.startswith("global_") or k.startswith("buffer_"))
     ds = sum(v for k, v in c.items() if k.startswith("ds_"))
     ex = sum(v for k, v in c.items() if "saveexec" in k or k.startswith("s_or_b64") or k.startswith("s_andn2_b64"))
-    print(f"MAXV={maxv} LM={lm} EXT={ext}: vgpr {info.get('NumVgprs')} scratch {info.get('ScratchSize')} "
+    print(f"{label}: vgpr {info.get('NumVgprs')} scratch {info.get('ScratchSize')} "
           f"code {info.get('codeLenInByte')} insts {len(ins)} scratch_ops {scr} vmem {vm} ds {ds} "
           f"exec_ops {ex} v_mov {c['v_mov_b32_e32']} cndmask {c['v_cndmask_b32_e32'] + c['v_cndmask_b32_e64']}")
