@@ -73,7 +73,7 @@ class Params(C.Structure):
                 ("ns_area_light", C.c_int32), ("samples_per_batch", C.c_int32),
                 ("max_tolerance", C.c_float), ("direct_hemisphere_sample", C.c_int32),
                 ("lens_radius", C.c_double), ("focal_distance", C.c_double),
-                ("reserved", C.c_int32 * 4)]
+                ("infinite_lights", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 INTEGRATOR_BDPT, INTEGRATOR_PT = 0, 1
@@ -364,7 +364,8 @@ class BidirectionalPathTracer:
     def __init__(self, scene: Scene, width: int, height: int, spp: int, max_depth: int,
                  seed: int = 5489, device: int = 0, samples_per_lane: int = 0,
                  collect_stats: bool = False, pipeline: int = PIPELINE_AUTO,
-                 russian_roulette: bool = False, _pt: Optional[dict] = None):
+                 russian_roulette: bool = False, infinite_lights: bool = False,
+                 _pt: Optional[dict] = None):
         self.lib = load_library()
         self.scene = scene
         self.width, self.height, self.spp, self.max_depth = width, height, spp, max_depth
@@ -374,6 +375,8 @@ class BidirectionalPathTracer:
         p.collect_stats = 1 if collect_stats else 0
         p.pipeline = pipeline
         p.russian_roulette = 1 if russian_roulette else 0
+        # ambient (hemisphere) and directional lights under BDPT; off: rejected
+        p.infinite_lights = 1 if infinite_lights else 0
         if _pt is not None:
             p.integrator = INTEGRATOR_PT
             p.ns_area_light = _pt["ns_area_light"]

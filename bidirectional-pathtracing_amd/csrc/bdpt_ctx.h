@@ -18,7 +18,8 @@ namespace bdpt {
 
 struct Ctx {
   HostScene hs;
-  bool ext = false;            // environment light or Russian roulette: the EXT kernels
+  int ext = 0;                 // kernel flavour (kernel_flavour, bdpt_scene.h): 1 environment light or
+                               // Russian roulette, 2 hemisphere / directional lights as well
   bdpt_params prm;
   int device = 0;
   hipStream_t own = nullptr, stream = nullptr;
@@ -99,7 +100,7 @@ inline SceneView view_of(const Ctx* c, int LM) {
   S.lstack = nullptr;
   S.cam = c->hs.cam;
   const HostScene& hs = c->hs;
-  S.env.light = hs.env_light;
+  S.env.light = hs.esc_light;
   S.env.w = hs.env_w;
   S.env.h = hs.env_h;
   const size_t np = (size_t)hs.env_w * hs.env_h;

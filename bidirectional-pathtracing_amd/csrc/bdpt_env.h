@@ -108,4 +108,29 @@ BDPT_HD f3 env_sample_dir(const EnvView& E, Rng& g, f3* w, float* pdf) {
   return env_bilerp(E, xf, yf);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Hemisphere (ambient) and directional lights under BDPT: the environment light's
+// machinery with a uniform hemisphere about +y, or one delta direction, in place of the tables.
+// sample_L's direction w (toward the light), its pdf and radiance: InfiniteHemisphereLight
+// (light.cpp:62-70, two uniforms, pdf 1/2pi) or DirectionalLight (light.cpp:17-23: dirToLight, no
+// uniform; its pdf 1 stands for the delta, which cancels between the strategies that sample it).
+BDPT_HD float hemi_pdf() { return (float)(1.0 / (2.0 * 3.14159265358979323)); }   // bdpt_pt.h light_sample_L's constant
+BDPT_HD f3 inf_sample_dir(const DLight& L, Rng& g, f3* w, float* pdf) {
+  if (L.type == LIGHT_DIR) {
+    *w = mk3(L.dir[0], L.dir[1], L.dir[2]);
+    *pdf = 1.0f;
+  } else {
+    const float Xi1 = rng_next(g);
+    const float Xi2 = rng_next(g);
+    float c, s;
+    cos_sin_2pi(Xi2, &c, &s);
+    const float st = sqrtf(fmaxf(0.0f, 1.0f - Xi1 * Xi1));
+    *w = mk3(st * c, Xi1, -(st * s));
+    *pdf = hemi_pdf();
+  }
+  return mk3(L.rad[0], L.rad[1], L.rad[2]);
+}
+// The hemisphere light seen along direction u (toward it): its radiance above the horizon
+BDPT_HD f3 hemi_radiance(const DLight& L, f3 u) { return u.y > 0.0f ? mk3(L.rad[0], L.rad[1], L.rad[2]) : splat3(0); }
+
 }  // namespace bdpt

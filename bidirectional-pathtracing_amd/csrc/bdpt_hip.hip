@@ -317,7 +317,7 @@ struct ConnState {
 // needs a visibility ray is pushed (ballot + mbcnt compaction) into the wave's LDS ring, and
 // whenever 64 are queued the wave traces them together. PA: the path accessor (PathsInRegs over the
 // lane's private Paths).
-template <int LM, bool EXT, bool STATS, class PA>
+template <int LM, int EXT, bool STATS, class PA>
 __device__ __forceinline__ void connect_sample(const KParams& kp, WaveQ& q, const PA& PP, Rng& g, int nE, int nL,
                                                int lane, float inv, ConnState& cs, Counters& cnt) {
 #ifdef BDPT_PHASE_PROF
@@ -448,9 +448,10 @@ __device__ __forceinline__ void flush_stats(unsigned long long* stats, int lane,
 
 // LM (LDS mode): 0 = scene read from HBM/L2; 1 = whole BVH + geometry staged in LDS by every
 // block; 2 = the top n_top BFS-ordered nodes (the part every ray traverses) staged in LDS.
-// EXT: environment light and/or Russian roulette; EXT = false is the reference-only
-// path with no trace of either in the generated code.
-template <int MAXV, bool STATS, int LM, bool EXT>
+// EXT, the kernel flavour: 1 = environment light and/or Russian roulette; 0 is the
+// reference-only path with no trace of either in the generated code; 2 = flavour 1 plus hemisphere
+// and directional lights (bdpt_params.infinite_lights, §9a), of which 0 and 1 hold no trace.
+template <int MAXV, bool STATS, int LM, int EXT>
 __global__ __launch_bounds__(kBlock, kMinWaves) void k_bdpt_sample(KParams kp) {
   // One dynamic LDS array: [wave queues][optional scene / treelet copy]
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -672,7 +673,7 @@ int pick_lm(Ctx* c, KParams& kp, size_t* lds) {
   return lm;
 }
 
-template <int MAXV, bool STATS, bool EXT>
+template <int MAXV, bool STATS, int EXT>
 int launch_lm(Ctx* c, KParams& kp) {
   size_t lds = 0;
   const int lm = pick_lm(c, kp, &lds);
@@ -684,8 +685,9 @@ int launch_lm(Ctx* c, KParams& kp) {
 
 template <int MAXV>
 int launch_maxv(Ctx* c, KParams& kp) {
-  if (c->ext) return c->prm.collect_stats ? launch_lm<MAXV, true, true>(c, kp) : launch_lm<MAXV, false, true>(c, kp);
-  return c->prm.collect_stats ? launch_lm<MAXV, true, false>(c, kp) : launch_lm<MAXV, false, false>(c, kp);
+  if (c->ext == 2) return c->prm.collect_stats ? launch_lm<MAXV, true, 2>(c, kp) : launch_lm<MAXV, false, 2>(c, kp);
+  if (c->ext) return c->prm.collect_stats ? launch_lm<MAXV, true, 1>(c, kp) : launch_lm<MAXV, false, 1>(c, kp);
+  return c->prm.collect_stats ? launch_lm<MAXV, true, 0>(c, kp) : launch_lm<MAXV, false, 0>(c, kp);
 }
 
 template <bool STATS>
@@ -778,7 +780,7 @@ int bdpt_create(const bdpt_scene_desc* scene, const bdpt_params* params, void** 
   if (c->pt && (p.ns_area_light < 0 || p.samples_per_batch < 0 || p.lens_radius < 0)) {
     g_err = "invalid PathTracer settings"; delete c; return BDPT_E_INVALID;
   }
-  int rc = build_host_scene(scene, c->hs, g_err, c->pt);
+  int rc = build_host_scene(scene, c->hs, g_err, c->pt, p.infinite_lights != 0);
   if (rc) { delete c; return rc; }
   // host-side shape check before anything runs: each tree holds whole nodes of the stride its
   // kernels read (hs.tree(lm_width(LM)) is what view_of hands the LDS mode LM)
@@ -790,7 +792,7 @@ int bdpt_create(const bdpt_scene_desc* scene, const bdpt_params* params, void** 
       return BDPT_E_INVALID;
     }
   }
-  c->ext = c->hs.env_light >= 0 || p.russian_roulette != 0;
+  c->ext = kernel_flavour(c->hs, p.russian_roulette != 0);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     g_err = "no HIP device";

@@ -27,15 +27,19 @@ struct LightSample {
   f3 pos, n, zh, alpha;
   float dir_pdf;
   float fwd;   // point_pdf / nL (the MIS denominator of the light end in environment scenes)
-  bool env;    // environment light: n = zh = -w, pos unused
+  bool env;    // environment (or, §9a, hemisphere / directional) light: n = zh = -w, pos unused
+  bool delta;  // directional light: no escaped ray reaches it (read by the infinite-light kernels only)
 };
 
 // A vertex as the path store holds it: the shading axis zh is not stored (it is zaxis(n), or n
 // itself for an environment vertex, and is recomputed where a connection reads it), and in the
-// reference-only kernels (EXT = false) the connectability flag rides in bit 16 of the material
+// reference-only kernels (EXT = 0) the connectability flag rides in bit 16 of the material
 // word, so a vertex is 12 dwords (48 B) instead of 16; EXT kernels keep cq (the roulette
 // probability of a connectable vertex) as a 13th dword. The private segment is lane-interleaved
 // per dword, so the dwords a kernel never touches cost no traffic.
+// EXT is the kernel flavour: 0 reference-only; 1 environment map and / or roulette (§9); 2 the
+// same plus hemisphere and directional lights (§9a). Code written `EXT ? ... : ...` serves 1 and 2;
+// what only flavour 2 has is behind `EXT >= 2`, so flavours 0 and 1 compile to what they were.
 struct VtxS {
   f3 pos;
   float fwd;
@@ -46,13 +50,13 @@ struct VtxS {
   float cq;   // EXT only
 };
 BDPT_HD int vs_mat(const VtxS& s) { return (int)(short)(s.mb & 0xffff); }
-template <bool EXT>
+template <int EXT>
 BDPT_HD void vtx_store(VtxS& s, const Vtx& v) {
   s.pos = v.pos; s.fwd = v.fwd; s.n = v.n; s.gp = v.gp; s.alpha = v.alpha;
   s.mb = (v.mat & 0xffff) | (!EXT && v.cq > 0.0f ? 0x10000 : 0);
   if (EXT) s.cq = v.cq;
 }
-template <bool EXT>
+template <int EXT>
 BDPT_HD Vtx vtx_load(const VtxS& s) {
   Vtx v;
   v.pos = s.pos; v.fwd = s.fwd; v.n = s.n; v.gp = s.gp; v.alpha = s.alpha;
@@ -75,7 +79,8 @@ struct Paths {
   VtxS E[MAXV];       // E[k] at index k-2 (k >= 2): eye hits
   VtxS L[MAXV + 1];   // L[k] at index k-1 (k >= 1): L[1] = light vertex, then hits
   int nE, nL;        // path sizes including v0, v1 (reference's vector sizes)
-  DeltaMask<MAXV> dE, dL;   // delta-BSDF bit masks: bit k set <=> E[k] / L[k] is_delta()
+  DeltaMask<MAXV> dE, dL;   // delta-BSDF bit masks: bit k set <=> E[k] / L[k] is_delta(); bit 0 of dL:
+                            // L[1] is on a directional light (infinite-light kernels, §9a)
   DeltaMask<MAXV> cE, cL;   // connectable vertices: bit k set <=> E[k] / L[k] has cq > 0
   DeltaMask<MAXV> sE;       // s = 0 sources: bit k set <=> E[k] is on an emitter or the environment
   float l1_dir_pdf;
@@ -175,6 +180,7 @@ BDPT_HD LightSample light_sample_point(const DLight& l, int nlights, Rng& g, f3 
   s.zh = zaxis(s.n);
   s.fwd = lpp;
   s.env = false;
+  s.delta = false;
   *lpp_out = lpp;
   return s;
 }
@@ -194,6 +200,24 @@ BDPT_HD LightSample env_sample_point(const SceneView& S, Rng& g, f3 p) {
   s.alpha = divs(rad, lpp);
   s.fwd = lpp;
   s.env = true;
+  s.delta = false;
+  return s;
+}
+// The same for a hemisphere or directional light L: w from inf_sample_dir.
+BDPT_HD LightSample inf_sample_point(const SceneView& S, const DLight& L, Rng& g, f3 p) {
+  LightSample s;
+  f3 w;
+  float pw;
+  const f3 rad = inf_sample_dir(L, g, &w, &pw);
+  const float lpp = pw / (float)S.nlights;
+  s.pos = p;
+  s.n = neg(w);
+  s.zh = s.n;
+  s.dir_pdf = 1.0f / L.area;
+  s.alpha = divs(rad, lpp);
+  s.fwd = lpp;
+  s.env = true;
+  s.delta = L.type == LIGHT_DIR;
   return s;
 }
 
@@ -247,7 +271,7 @@ BDPT_HD EyeSample camera_sample(const DCam& c, int W, int H, f3 p) {
 // i, j: reference vertex indices; ls: fresh light sample (j == 1); es: camera sample (i == 1);
 // dc, dist: normalize(vl - ve) and |vl - ve| of the connection (j >= 1), which are exactly the
 // endpoint-step directions the reference recomputes (normalize(-v) == -normalize(v) in IEEE).
-template <bool EXT = false, class PA>
+template <int EXT = 0, class PA>
 BDPT_HD float mis_weight(const SceneView& S, const PA& P, const Vtx* ev, const Vtx* lv, int i, int j,
                          const LightSample& ls, const EyeSample& es, int eye_light, f3 dc, float dist) {
   float ge = 0.0f, gl = 0.0f;
@@ -260,6 +284,10 @@ BDPT_HD float mis_weight(const SceneView& S, const PA& P, const Vtx* ev, const V
       float p = EL.type == LIGHT_POINT ? 1.0f
                 : (EXT && EL.type == LIGHT_ENV) ? env_pdf_dir(S.env, neg(cur.n)) / (float)S.nlights
                                                 : 1.0f / EL.area;
+      // §9a: a hemisphere light's density of this direction; and the light choice's 1 / nL on an
+      // emitter too (the reference leaves it out, which only one-light scenes forgive), as every
+      // other strategy of these kernels that samples the light carries it
+      if (EXT >= 2) p = (EL.type == LIGHT_HEMI ? hemi_pdf() : p) / (EL.type == LIGHT_ENV ? 1.0f : (float)S.nlights);
       nom = p * 1.0f;
     } else {
       f3 pzh = j == 1 ? ls.zh : lv->zh;
@@ -276,7 +304,8 @@ BDPT_HD float mis_weight(const SceneView& S, const PA& P, const Vtx* ev, const V
       const float revg = EXT ? step_gx(v.pos, v.n, false, cur.pos, cur.zh, cenv, &dr)
                              : step_g(v.pos, v.n, cur.pos, cur.zh, &dr);   // g of the step E[i-1] <- E[i]
       f3 dw = cenv ? cur.n : normalize(sub(v.pos, cur.pos));
-      float dp = light_dir_pdf(S.lights[eye_light], neg(dw));
+      // (an env vertex's light — map or, §9a, hemisphere — emits from the disk: planar density 1 / area)
+      float dp = (EXT >= 2 && cenv) ? 1.0f / S.lights[eye_light].area : light_dir_pdf(S.lights[eye_light], neg(dw));
       below = mis_horner(((dp * 1.0f) * revg) / v.fwd, !((P.dE >> (i - 2)) & 3u), v.gp);
     }
     // delta(E[i]) || delta(E[i-1]); an escaped camera ray (i = 2) has no camera-connection strategy
@@ -284,14 +313,16 @@ BDPT_HD float mis_weight(const SceneView& S, const PA& P, const Vtx* ev, const V
     ge = mis_horner(nom / cur.fwd, t, below);
   }
   if (j >= 1) {
-    if (EXT && j == 1 && S.env.light >= 0) {
-      // environment scenes: the light end of (i, 1) is the fresh sample itself
+    if (EXT && j == 1 && (EXT >= 2 || S.env.light >= 0)) {
+      // environment scenes: the light end of (i, 1) is the fresh sample itself; so it
+      // is in every scene of the infinite-light kernels, where the term is off for a directional
+      // light's sample: no eye subpath ends on a delta direction (§9a)
       f3 dw;
       float g;
       if (ls.env) { dw = dc; g = 1.0f; }
       else g = step_g(ls.pos, ls.n, i == 1 ? es.pos : ev->pos, i == 1 ? es.zh : ev->zh, &dw);
       float p = i <= 1 ? es.dir_pdf * 1.0f : pdf_b(S.mats[ev->mat], ev->n, ev->zh, dw) * ev->cq;
-      gl = mis_horner((p * g) / ls.fwd, true, 0.0f);
+      gl = mis_horner((p * g) / ls.fwd, !(EXT >= 2 && ls.delta), 0.0f);
     } else {
       const Vtx& cur = *lv;   // j == 1: the original L[1], not the fresh sample (quirk 5)
       f3 pzh = i == 1 ? es.zh : ev->zh;
@@ -312,7 +343,7 @@ BDPT_HD float mis_weight(const SceneView& S, const PA& P, const Vtx* ev, const V
 }
 
 // Path accessor over one lane's Paths (megakernel, host tests).
-template <int MAXV, bool EXT>
+template <int MAXV, int EXT>
 struct PathsInRegs {
   const Paths<MAXV>& P;
   DeltaMask<MAXV> dE, dL;
@@ -343,7 +374,7 @@ struct WalkState {
 
 // Starts one pixel-sample's walk: the camera ray (raytrace_pixel's jitter, bidirection.cpp:515-524)
 // and the light vertex L[1] with the light walk's first ray (sample_light_ray, :105-118).
-template <int MAXV, bool EXT = false>
+template <int MAXV, int EXT = 0>
 BDPT_HD void walk_begin(const SceneView& S, const SampleParams& sp, Paths<MAXV>& P, Counters& cnt, Rng& g,
                         WalkState<MAXV>& w, int x, int y, uint32_t sample) {
   rng_init(g, sp.seed, (uint32_t)(x + y * sp.W), sample);
@@ -358,8 +389,8 @@ BDPT_HD void walk_begin(const SceneView& S, const SampleParams& sp, Paths<MAXV>&
   // light vertex L[1] and the light walk's first ray, drawn before the eye walk and kept in the path
   // store (read back when the light walk starts), so the ~17 registers of the light sample are not
   // live across the eye walk's traversals (drawing them at the switch instead spilled more).
-  bool l1env = false;
-  float mis_p = 0.0f;   // L[1]'s MIS point density (differs from lpp only for the env light)
+  bool l1env = false, l1dir = false;   // l1dir: L[1] is on a directional light (§9a)
+  float mis_p = 0.0f;  // L[1]'s MIS point density (differs from lpp only for the env light)
   auto sample_light = [&](Rng& gl, f3& lo, f3& ld, f3& ln, f3& alpha1, float& ldp) {
     rng_stream(gl, 1);
     int lid = (int)(rng_next(gl) * (float)S.nlights);
@@ -367,13 +398,19 @@ BDPT_HD void walk_begin(const SceneView& S, const SampleParams& sp, Paths<MAXV>&
     const DLight& L0 = S.lights[lid];
     f3 lrad = mk3(L0.rad[0], L0.rad[1], L0.rad[2]);
     float lpp, mis_dir;
-    if (EXT && L0.type == LIGHT_ENV) {
+    if (EXT && (L0.type == LIGHT_ENV || (EXT >= 2 && L0.type >= LIGHT_HEMI))) {
       // sample_Le of the environment light: direction by sample_L's importance
-      // sampling, origin uniform on the disk of radius R facing -w, tangent to the bounding sphere
+      // sampling, origin uniform on the disk of radius R facing -w, tangent to the bounding sphere;
+      // a hemisphere or directional light (§9a) the same with its own sample_L
       f3 w;
       float pw;
-      lrad = env_sample_dir(S.env, gl, &w, &pw);
-      cnt.env_s++;
+      if (EXT >= 2 && L0.type != LIGHT_ENV) {
+        lrad = inf_sample_dir(L0, gl, &w, &pw);
+        l1dir = L0.type == LIGHT_DIR;
+      } else {
+        lrad = env_sample_dir(S.env, gl, &w, &pw);
+        cnt.env_s++;
+      }
       const float u1 = rng_next(gl), u2 = rng_next(gl);
       const float r = S.env.rad * sqrtf(u1);
       float c, sn;
@@ -426,7 +463,7 @@ BDPT_HD void walk_begin(const SceneView& S, const SampleParams& sp, Paths<MAXV>&
     v1.n = ln;
     v1.zh = l1env ? ln : zaxis(ln);
     v1.alpha = alpha1;
-    v1.mat = l1env ? (int)MAT_ENV_V : -1;
+    v1.mat = l1env ? ((EXT >= 2 && l1dir) ? (int)MAT_DIRL_V : (int)MAT_ENV_V) : -1;
     v1.gp = 0; v1.cq = 0;
     v1.fwd = mis_p;   // light_constants' L[1] value (set here for the fused walk)
     vtx_store<EXT>(P.L[0], v1);
@@ -465,7 +502,7 @@ BDPT_HD void walk_begin(const SceneView& S, const SampleParams& sp, Paths<MAXV>&
 // One iteration of the fused walk: trace the next ray, store the vertex it hits (with its MIS
 // constants), sample the continuation. Returns true once the light subpath has ended (both
 // subpaths and P.nE / P.nL / P.dE / P.dL complete).
-template <int MAXV, int LM = 0, bool EXT = false>
+template <int MAXV, int LM = 0, int EXT = 0>
 BDPT_HD bool walk_step(const SceneView& S, const SampleParams& sp, Paths<MAXV>& P, Counters& cnt, Rng& g,
                        WalkState<MAXV>& w) {
   f3 ro = w.ro, rd = w.rd, prev_n = w.prev_n, nalpha = w.nalpha;
@@ -632,9 +669,13 @@ BDPT_HD bool walk_step(const SceneView& S, const SampleParams& sp, Paths<MAXV>& 
       ro = P.L[0].pos; rd = P.l1_d; prev_n = P.L[0].n;
       nalpha = next_alpha(P.L[0].alpha, prev_n, rd, splat3(1.0f), P.l1_pdf);
       const float mis_p = P.L[0].fwd;
-      l1env = vs_mat(P.L[0]) == (int)MAT_ENV_V;
+      l1env = EXT >= 2 ? vs_mat(P.L[0]) <= (int)MAT_ENV_V : vs_mat(P.L[0]) == (int)MAT_ENV_V;
       rmin = BDPT_EPS_F; rmax = INFINITY;
       i = 2; count = 0; dm = 0; cm = 0;
+      // §9a: no eye subpath ends on a directional light. Bit 0 of the light mask (the step from
+      // L[1] to the light's own sampling, which only L[2]'s prefix reads) switches that strategy
+      // off the way a delta vertex would, and leaves the (i, 1) connections to L[2] alone.
+      if (EXT >= 2 && vs_mat(P.L[0]) == (int)MAT_DIRL_V) dm = 1;
       pv_mat = -1; pv_fwd = mis_p; pv_gp = 0.0f; pv_q = 1.0f;   // the light vertex L[1]
       }
     }
@@ -651,7 +692,7 @@ BDPT_HD bool walk_step(const SceneView& S, const SampleParams& sp, Paths<MAXV>& 
 // eye walk ends starts its light walk in the next iteration, so a wave iterates
 // max(|E| + |L|) times instead of max |E| + max |L|. The RNG sub-streams (eye walk: 0, light
 // sample + walk: 1) make the interleaving invisible in the results.
-template <int MAXV, int LM = 0, bool EXT = false>
+template <int MAXV, int LM = 0, int EXT = 0>
 BDPT_HD void prepare_sample(const SceneView& S, const SampleParams& sp, Paths<MAXV>& P, Counters& cnt, Rng& g,
                             int x, int y, uint32_t sample) {
   WalkState<MAXV> w;
@@ -676,7 +717,7 @@ BDPT_HD bool can_connect(const Vtx& v) { return v.cq > 0.0f; }
 // ev_pre / lv_pre: E[i] / L[j] already loaded by the caller (kept across the megakernel's inner
 // connection loop), or null.
 // ec: environment-table read counters (stats builds), or null.
-template <bool EXT = false, class PA>
+template <int EXT = 0, class PA>
 BDPT_HD int make_conn(const SceneView& S, const SampleParams& sp, const PA& P, Rng& g, int i, int j, Conn& cn,
                       const Vtx* ev_pre = nullptr, const Vtx* lv_pre = nullptr, Counters* ec = nullptr) {
   const f3 cam = mk3(S.cam.pos[0], S.cam.pos[1], S.cam.pos[2]);
@@ -684,6 +725,7 @@ BDPT_HD int make_conn(const SceneView& S, const SampleParams& sp, const PA& P, R
   Vtx ev, lv;
   LightSample ls;
   ls.env = false;
+  ls.delta = false;
   EyeSample es;
   es.x = -1; es.y = -1;
   cn.splat = -1;
@@ -691,13 +733,21 @@ BDPT_HD int make_conn(const SceneView& S, const SampleParams& sp, const PA& P, R
   if (j == 0) {
     if (eye_cam) return CONN_NONE;
     if (EXT && is_env(ev)) {   // an escaped eye ray: the environment light contains it (§9)
-      const f3 c = env_radiance(S.env, neg(ev.n));
-      if (ec) ec->env_l++;
+      f3 c;
+      const bool hemi = EXT >= 2 && S.lights[S.env.light].type == LIGHT_HEMI;
+      if (hemi) {
+        // §9a: the sky above the horizon; an escaped camera ray (i = 2) sees none of it, as the
+        // reference's PathTracer looks up only the environment map there
+        c = i >= 3 ? hemi_radiance(S.lights[S.env.light], neg(ev.n)) : splat3(0);
+      } else {
+        c = env_radiance(S.env, neg(ev.n));
+        if (ec) ec->env_l++;
+      }
       f3 contrib = mul(mul(ev.alpha, splat3(1.0f)), c);
       float w = 0;
       if (norm(contrib) > BDPT_EPS_F) {
         w = mis_weight<EXT>(S, P, &ev, &lv, i, 0, ls, es, S.env.light, splat3(0), 0);
-        if (ec) ec->env_p++;   // the j = 0 weight's env_pdf_dir
+        if (ec && !hemi) ec->env_p++;   // the j = 0 weight's env_pdf_dir
       }
       cn.val = muls(contrib, w);
       return CONN_DIRECT;
@@ -708,7 +758,8 @@ BDPT_HD int make_conn(const SceneView& S, const SampleParams& sp, const PA& P, R
     if (!(norm(c) > BDPT_EPS_F)) return CONN_NONE;
     int eye_light = -1;
     for (int l = 0; l < S.nlights; l++)
-      if ((!EXT || S.lights[l].type != LIGHT_ENV) && light_contains(S.lights[l], ev.pos)) { eye_light = l; break; }
+      if ((!EXT || S.lights[l].type != LIGHT_ENV) && (EXT < 2 || S.lights[l].type < LIGHT_ENV) &&
+          light_contains(S.lights[l], ev.pos)) { eye_light = l; break; }
     if (eye_light < 0) return CONN_NONE;
     f3 prevp = i == 2 ? cam : P.e(i - 1).pos;
     f3 wi = normalize(sub(ev.pos, prevp));
@@ -735,6 +786,9 @@ BDPT_HD int make_conn(const SceneView& S, const SampleParams& sp, const PA& P, R
       if (eye_cam) return CONN_NONE;   // no camera connection to a vertex at infinity (§9)
       ls = env_sample_point(S, g, epos);
       if (ec) ec->env_s++;
+    } else if (EXT >= 2 && S.lights[id].type >= LIGHT_HEMI) {   // hemisphere / directional (§9a)
+      if (eye_cam) return CONN_NONE;
+      ls = inf_sample_point(S, S.lights[id], g, epos);
     } else {
       float lp;
       ls = light_sample_point(S.lights[id], S.nlights, g, epos, &lp);
@@ -796,7 +850,7 @@ BDPT_HD int make_conn(const SceneView& S, const SampleParams& sp, const PA& P, R
 
 // One pixel-sample, connections resolved in the reference's (i, j) order (host/test use; the
 // device kernel defers the connection rays to a wave-compacted queue instead).
-template <int MAXV, int LM = 0, bool EXT = false, class Sink>
+template <int MAXV, int LM = 0, int EXT = 0, class Sink>
 BDPT_HD f3 render_sample(const SceneView& S, const SampleParams& sp, Paths<MAXV>& P, Counters& cnt,
                          int x, int y, uint32_t sample, Sink& sink) {
   Rng g;

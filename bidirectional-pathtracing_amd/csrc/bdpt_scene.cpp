@@ -373,7 +373,7 @@ float i2f(int v) {
 
 }  // namespace
 
-int build_host_scene(const bdpt_scene_desc* d, HostScene& out, std::string& err, bool pt) {
+int build_host_scene(const bdpt_scene_desc* d, HostScene& out, std::string& err, bool pt, bool inf) {
   if (!d || d->nprim <= 0 || !d->prim_type || !d->prim_geom || !d->prim_mat) {
     err = "scene has no primitives";
     return BDPT_E_INVALID;
@@ -402,9 +402,21 @@ int build_host_scene(const bdpt_scene_desc* d, HostScene& out, std::string& err,
   }
   // lights (light.cpp:102-284)
   out.lights.clear();
+  out.inf_lights = 0;
+  int hemi_light = -1, n_escape = d->envmap ? 1 : 0;   // lights an escaped ray can reach
   for (int i = 0; i < d->nlight; i++) {
     const bdpt_light& l = d->lights[i];
-    if ((l.type == BDPT_LIGHT_HEMISPHERE || l.type == BDPT_LIGHT_DIRECTIONAL) && !pt) {
+    const bool is_inf = l.type == BDPT_LIGHT_HEMISPHERE || l.type == BDPT_LIGHT_DIRECTIONAL;
+    if (is_inf && !pt && inf) {
+      // bdpt_params.infinite_lights; the walk knows one escape-visible light
+      out.inf_lights++;
+      if (l.type == BDPT_LIGHT_HEMISPHERE) { hemi_light = i; n_escape++; }
+      if (n_escape > 1) {
+        err = "BDPT renders at most one light that an escaped ray can reach (the environment map or one ambient "
+              "light); this scene has more: use the PathTracer integrator";
+        return BDPT_E_UNSUPPORTED;
+      }
+    } else if (is_inf && !pt) {
       err = "ambient (InfiniteHemisphereLight) and directional lights only implement sample_L: the BDPT light "
             "API asserts (light.cpp:25-51,72-98); use the PathTracer integrator";
       return BDPT_E_UNSUPPORTED;
@@ -520,7 +532,16 @@ int build_host_scene(const bdpt_scene_desc* d, HostScene& out, std::string& err,
     };
     guide(fmarg, h, gm);
     for (int j = 0; j < h; j++) guide(fcond + (size_t)w * j, w, gc);
-    // bounding sphere of the primitives (the emission disk's radius and centre)
+    DLight L;
+    std::memset(&L, 0, sizeof L);
+    L.type = LIGHT_ENV;
+    out.env_light = (int)out.lights.size();
+    out.lights.push_back(L);
+  }
+  out.esc_light = out.env_light >= 0 ? out.env_light : hemi_light;
+  if (out.env_light >= 0 || out.inf_lights > 0) {
+    // bounding sphere of the primitives (the emission disk's radius and centre) for the lights at
+    // infinity: the environment light and the hemisphere / directional lights BDPT accepted
     double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int i = 0; i < n; i++)
       for (int k = 0; k < 3; k++) { mn[k] = std::min(mn[k], pb[i].mn[k]); mx[k] = std::max(mx[k], pb[i].mx[k]); }
@@ -531,12 +552,9 @@ int build_host_scene(const bdpt_scene_desc* d, HostScene& out, std::string& err,
     }
     const double R = std::sqrt(ext2) / 2;
     out.env_rad = (float)R;
-    DLight L;
-    std::memset(&L, 0, sizeof L);
-    L.type = LIGHT_ENV;
-    L.area = (float)(PI_D * R * R);
-    out.env_light = (int)out.lights.size();
-    out.lights.push_back(L);
+    for (DLight& L : out.lights)
+      if (L.type == LIGHT_ENV || (out.inf_lights > 0 && (L.type == LIGHT_HEMI || L.type == LIGHT_DIR)))
+        L.area = (float)(PI_D * R * R);
   }
   // the reference's tree: its DFS leaf order is the tie-break key of every primitive
   Builder R;

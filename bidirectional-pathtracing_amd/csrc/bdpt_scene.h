@@ -54,7 +54,17 @@ struct HostScene {
                               // guide tables (int32 bits): marginal[gm+1] | per row conditional[h*(gc+1)]
   int env_gm = 0, env_gc = 0; // guide-table cells (powers of two)
   float env_c[3] = {0, 0, 0}, env_rad = 0;
+  // hemisphere / directional lights accepted under BDPT (bdpt_params.infinite_lights, DESIGN.md
+  // §9a): how many, and the one light an escaped ray reaches: env_light, or the hemisphere light
+  int inf_lights = 0;
+  int esc_light = -1;
 };
+
+// Which k_bdpt_sample flavour renders a scene (the EXT template parameter, bdpt_paths.h): 2 with an
+// accepted hemisphere / directional light, 1 with an environment map or roulette, else 0.
+inline int kernel_flavour(const HostScene& hs, bool roulette) {
+  return hs.inf_lights > 0 ? 2 : (hs.env_light >= 0 || roulette) ? 1 : 0;
+}
 
 constexpr int kTopNodes = 1024;
 // Spatial splits in the device tree (SBVH, bdpt_scene.cpp SahBuilder): tried at a node whose best
@@ -84,6 +94,7 @@ inline int flat_prims(const HostScene& hs, uint32_t* sph) {
 
 // Returns BDPT_OK or an error code; err receives a message.
 // pt: the scene is for the unidirectional PathTracer (microfacet materials allowed).
-int build_host_scene(const bdpt_scene_desc* d, HostScene& out, std::string& err, bool pt = false);
+// inf: under BDPT, accept hemisphere and directional lights (bdpt_params.infinite_lights).
+int build_host_scene(const bdpt_scene_desc* d, HostScene& out, std::string& err, bool pt = false, bool inf = false);
 
 }  // namespace bdpt

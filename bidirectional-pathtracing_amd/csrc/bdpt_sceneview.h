@@ -13,8 +13,11 @@ namespace bdpt {
 enum { MAT_DIFFUSE = 0, MAT_EMISSION = 1, MAT_MIRROR = 2, MAT_GLASS = 3, MAT_REFRACTION = 4, MAT_MICROFACET = 5 };
 // Vtx::mat of a vertex without BSDF: -1 camera / area or point light vertex, MAT_ENV_V a vertex
 // of the environment light (an escaped eye ray, or an env light subpath's first vertex).
-enum { MAT_ENV_V = -2 };
-enum { LIGHT_AREA = 0, LIGHT_POINT = 1, LIGHT_ENV = 2, LIGHT_HEMI = 3, LIGHT_DIR = 4 };   // HEMI, DIR: PathTracer only
+// MAT_DIRL_V: the first vertex L[1] of a directional light's subpath (an env vertex whose light no
+// escaped ray reaches); stored only, the walk turns it into MAT_ENV_V semantics.
+enum { MAT_ENV_V = -2, MAT_DIRL_V = -3 };
+// HEMI, DIR: the PathTracer, and BDPT's infinite-light kernels (bdpt_params.infinite_lights, §9a)
+enum { LIGHT_AREA = 0, LIGHT_POINT = 1, LIGHT_ENV = 2, LIGHT_HEMI = 3, LIGHT_DIR = 4 };
 // Russian roulette (bdpt_params.russian_roulette): vertices with index i > BDPT_RR_MIN continue
 // with p_keep = min(1, |f| / pdf) (the rule commented out at bidirection.cpp:87-93).
 #define BDPT_RR_MIN 3
@@ -29,7 +32,7 @@ struct DMat {
 struct DLight {
   int type;
   float rad[3], pos[3], dir[3], dx[3], dy[3];
-  float area;                 // LIGHT_ENV: pi R^2 of the scene's bounding sphere (emission disk)
+  float area;                 // LIGHT_ENV, and HEMI / DIR under BDPT: pi R^2 of the scene's bounding sphere (emission disk)
   float fx[3], fy[3], fz[3];  // make_coord_space(dir)
 };
 
@@ -45,7 +48,8 @@ struct EnvView {
   const int* gcond;    // h*(gc+1): guide tables of the rows of cond
   int gm, gc;
   int w, h;
-  int light;           // index of the env light in the light list (-1: none)
+  int light;           // index of the light an escaped ray reaches (-1: none): the env light, or in the
+                       // infinite-light kernels a hemisphere light (the tables are then empty)
   float cx, cy, cz, rad;
 };
 struct DCam {

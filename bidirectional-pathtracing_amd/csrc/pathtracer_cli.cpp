@@ -2,7 +2,7 @@
 // in windowless mode, rendering through libbdpt_amd.so on MI355X GPUs.
 //
 //   pathtracer [-s spp] [-m max_depth] [-r W H] [-f out.png] [-p x y dx dy] [-t threads] [-c cam.txt]
-//              [-l n] [-e envmap.exr] [--rr] [-g gpus] [-S seed] [--dump-scene scene.json]
+//              [-l n] [-e envmap.exr] [--rr] [--infinite-lights] [-g gpus] [-S seed] [--dump-scene scene.json]
 //              [--pt [-a batch tol] [-H] [-b lens] [-d focal]] scene.dae
 //
 // Same flags and defaults as the reference (-s 1, -m 1, 800x600 when -r is absent; -t / -l are
@@ -10,7 +10,9 @@
 // over N devices (one context and one host thread per device) and sums the frames on the devices with
 // one RCCL reduce into device 0's (bdpt_reduce_frames, inside the timed region). -e loads an
 // environment map as the reference's -e does (load_exr, main.cpp:115-119) — under BDPT, which the
-// reference cannot run with it; --rr turns on Russian roulette (bidirection.cpp:87-93).
+// reference cannot run with it; --rr turns on Russian roulette (bidirection.cpp:87-93);
+// --infinite-lights lets BDPT render ambient and directional lights (bdpt_params.infinite_lights,
+// DESIGN.md §9a), which it otherwise rejects as the reference's BDPT cannot run them.
 // --pt selects the reference's unidirectional PathTracer (pathtracer.cpp:47-340) with its flags
 // -l, -a, -H, -b, -d (main.cpp:107-141); its -g N splits the frame into row bands (whole pixels).
 // Output: the tonemapped PNG and the "_rate.png" sampling-rate image, as render_to_file writes
@@ -47,6 +49,8 @@ void usage(const char* b) {
   printf("  -d  <FLOAT>      PathTracer: focal distance\n");
   printf("  -e  <PATH>       Path to environment map\n");
   printf("  --rr             Russian roulette on both subpaths\n");
+  printf("  --infinite-lights  BDPT: render ambient and directional lights (rejected without it;\n"
+         "                   --pt renders them too)\n");
   printf("  -c  <FILENAME>   Load camera settings file (Camera::dump_settings format)\n");
   printf("  -f  <FILENAME>   Image (.png) file to save output to\n");
   printf("  -r  <INT> <INT>  Width and height of output image\n");
@@ -74,7 +78,7 @@ int main(int argc, char** argv) {
   unsigned long long seed = 5489;
   std::string out, dump, scene, envpath, cam_settings;
   std::vector<int> devices;
-  bool rr = false, pt = false, hemi = false, stats = true;
+  bool rr = false, pt = false, hemi = false, stats = true, inf_lights = false;
   int nal = 1, batch = 32;
   float tol = 0.05f;
   double lens = 0.0, focal = 4.7;
@@ -110,6 +114,7 @@ int main(int argc, char** argv) {
     else if (a == "--dump-scene") { need(1); dump = argv[++i]; }
     else if (a == "-e") { need(1); envpath = argv[++i]; }
     else if (a == "--rr") rr = true;
+    else if (a == "--infinite-lights") inf_lights = true;
     else if (a == "--no-stats") stats = false;
     else if (a == "--tonemap") {
       need(4);
@@ -172,6 +177,7 @@ int main(int argc, char** argv) {
     p.width = w; p.height = h; p.spp = spp; p.max_depth = max_depth; p.seed = seed;
     p.device = g < (int)devices.size() ? devices[g] : g;
     p.russian_roulette = rr ? 1 : 0;
+    p.infinite_lights = inf_lights ? 1 : 0;
     p.collect_stats = count ? 1 : 0;
     if (pt) {
       p.integrator = BDPT_INTEGRATOR_PT;
@@ -222,6 +228,13 @@ int main(int argc, char** argv) {
     for (int g = 0; g < gpus; g++)
       if (rcs[g] != BDPT_OK) {
         fprintf(stderr, "[PathTracer] GPU %d: %s\n", g, errs[g].c_str());
+        if (rcs[g] == BDPT_E_UNSUPPORTED && !pt && !inf_lights)
+          for (int l = 0; l < desc.nlight; l++)
+            if (desc.lights[l].type == BDPT_LIGHT_HEMISPHERE || desc.lights[l].type == BDPT_LIGHT_DIRECTIONAL) {
+              fprintf(stderr, "[PathTracer] the scene has an ambient or directional light: pass --infinite-lights "
+                              "to render it with BDPT, or --pt for the PathTracer\n");
+              break;
+            }
         return false;
       }
     return true;

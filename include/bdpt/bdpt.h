@@ -23,16 +23,22 @@
  * Plain C types only: no torch, no HIP types in any signature (a stream is passed as void*).
  * Every call returns 0 (BDPT_OK) or a negative BDPT_E_* code; bdpt_last_error() gives the text.
  * No C++ exception crosses this boundary. Unsupported features that the reference can only
- * assert(0) on under BDPT (microfacet sample_pdf, advanced_bsdf.cpp:144-148; directional / spot /
- * sphere / mesh lights, light.cpp:25-51,168-194) are rejected at bdpt_create with
- * BDPT_E_UNSUPPORTED instead of aborting.
+ * assert(0) on under BDPT (microfacet sample_pdf, advanced_bsdf.cpp:144-148; ambient / directional /
+ * spot / sphere / mesh lights, light.cpp:25-51,72-98,168-194) are rejected at bdpt_create with
+ * BDPT_E_UNSUPPORTED instead of aborting (ambient and directional lights: unless
+ * bdpt_params.infinite_lights is set, below).
  *
  * Extensions beyond what the reference can run (semantics in DESIGN.md §9):
  *   - the environment light under BDPT (the reference's EnvironmentLight has sample_L / sample_dir
  *     but asserts in sample_Le / sample_Le_point / sample_pdf / contain_point,
  *     environment_light.cpp:182-208): bdpt_scene_desc.envmap, loaded by bdpt_exr_load (-e);
  *   - Russian roulette on both subpaths through PathVertex.q (bidirection.h:36, the rule commented
- *     out at bidirection.cpp:87-93): bdpt_params.russian_roulette.
+ *     out at bidirection.cpp:87-93): bdpt_params.russian_roulette;
+ *   - ambient (InfiniteHemisphereLight) and directional lights under BDPT (the reference's BDPT
+ *     light API prints "not ready" and asserts for them, light.cpp:25-51,72-98), with the
+ *     environment light's machinery: bdpt_params.infinite_lights. At most
+ *     one light that an escaped ray can reach — the environment map or one ambient light — per
+ *     scene; any number of directional lights.
  * And the reference's second integrator: the unidirectional PathTracer
  * (pathtracer.cpp:47-340 — NEE, adaptive sampling, thin lens, roulette at -m 0, the environment
  * light, MicrofacetBSDF), selected by bdpt_params.integrator = BDPT_INTEGRATOR_PT (ABI v3).
@@ -71,15 +77,18 @@ enum bdpt_mat_type {
 };
 
 /* Light kinds (src/scene/light.h). Only area and point lights have BDPT methods in the reference;
- * the environment light comes in through bdpt_scene_desc.envmap, never through this list. */
+ * ambient and directional lights render under BDPT with bdpt_params.infinite_lights; the
+ * environment light comes in through bdpt_scene_desc.envmap, never through this list. */
 enum bdpt_light_type {
   BDPT_LIGHT_AREA = 0, BDPT_LIGHT_POINT = 1,
   BDPT_LIGHT_OTHER = 2,       /* spot: rejected (SpotLight::sample_L leaves its outputs unset,
                                  light.cpp:163-166)                                            */
   BDPT_LIGHT_HEMISPHERE = 3,  /* an ambient light = InfiniteHemisphereLight (light.cpp:55-70):
-                                 PathTracer only (BDPT: sample_Le asserts, :72-77)             */
+                                 the PathTracer, and BDPT with bdpt_params.infinite_lights
+                                 (the reference's BDPT: sample_Le asserts, :72-77)              */
   BDPT_LIGHT_DIRECTIONAL = 4  /* DirectionalLight (light.cpp:11-23): `direction` = dirToLight, the
-                                 unit world direction towards the light; PathTracer only        */
+                                 unit world direction towards the light; the PathTracer, and
+                                 BDPT with bdpt_params.infinite_lights                          */
 };
 
 typedef struct bdpt_material {
@@ -158,7 +167,11 @@ typedef struct bdpt_params {
   int32_t direct_hemisphere_sample;  /* -H: hemisphere instead of light sampling            */
   double lens_radius;         /* -b (0: pinhole)                                             */
   double focal_distance;      /* -d (0 = 4.7)                                                */
-  int32_t reserved[4];
+  /* Was reserved[0]: the layout is unchanged and a caller that zeroes the reserved words gets the
+   * rejection it always got, so the ABI version stays 9. BDPT only; the PathTracer ignores it. */
+  int32_t infinite_lights;    /* 0: BDPT rejects BDPT_LIGHT_HEMISPHERE / _DIRECTIONAL with
+                                 BDPT_E_UNSUPPORTED; 1: it renders them         */
+  int32_t reserved[3];
 } bdpt_params;
 
 enum bdpt_integrator { BDPT_INTEGRATOR_BDPT = 0, BDPT_INTEGRATOR_PT = 1 };
