@@ -85,7 +85,10 @@ BDPT_HD bool sph_test(const float4 g0, f3 o, f3 d, float tmin, float tmax, float
 
 // ------------------------------------------------------------------------------------------------
 // BVH traversal (replaces BVHAccel::intersect, bvh.cpp:161-188; see header comment).
-constexpr int kStackMax = 64;
+#ifndef BDPT_STACK_MAX
+#define BDPT_STACK_MAX 64
+#endif
+constexpr int kStackMax = BDPT_STACK_MAX;   // variant builds may override (-DBDPT_STACK_MAX=...)
 // Register-stack entries of the megakernel's walk / connection-ray traversals (TravStack<K>).
 // Measured (Lucy stand-in 1080p / CBspheres / CBgems, Msamples/s): K 0: 440 / 438 / 273,
 // K 2: 465 / 452 / 284, K 4: 465 / 450 / 290 (walk 8 or connection 8: no further gain). Round 4,

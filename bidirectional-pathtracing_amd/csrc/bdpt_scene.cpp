@@ -350,6 +350,155 @@ struct SahBuilder {
     nodes[id].box = bb;
     return id;
   }
+
+  // Bottom-up repair of the finished binary tree by subtree reinsertion (Bittner, Hapala and Havran
+  // 2013, "Fast insertion-based optimization of bounding volume hierarchies"): the top-down build
+  // never revisits a split; here every subtree x is detached (its sibling takes their parent's
+  // place) and attached again beside the node y where the tree's total surface area grows least,
+  // area(y u x) + sum over y's ancestors a of (area(a u x) - area(a)); x's freed parent becomes the
+  // parent of (y, x). y is found best-first on the induced (ancestor) cost, which bounds every
+  // position below a node from below. The old position is a candidate, so no move raises the total
+  // area. Leaves are atomic (a spatial split's clipped leaf boxes stay as make_leaf stored them),
+  // the root keeps its node id and its two children are not moved. Nodes are visited by decreasing
+  // area (ties by id) in passes, until a pass moves nothing or kReinsertPasses; from the second pass
+  // on only nodes next to something that changed in the pass before (themselves, their parent,
+  // grandparent or sibling) are tried again. Afterwards leaf_prims is emitted again in the new DFS
+  // order (the primitive records follow it) and depth recomputed.
+  static constexpr int kReinsertPasses = 8;
+  static Box merged(const Box& a, const Box& b) {
+    Box r = a;
+    r.expand(b);
+    return r;
+  }
+  static bool same(const Box& a, const Box& b) {
+    for (int k = 0; k < 3; k++)
+      if (a.mn[k] != b.mn[k] || a.mx[k] != b.mx[k]) return false;
+    return true;
+  }
+  void reinsert_optimise(int root) {
+    const int N = (int)nodes.size();
+    if (nodes[root].l < 0) return;
+    std::vector<int> parent(N, -1);
+    for (int i = 0; i < N; i++)
+      if (nodes[i].l >= 0) { parent[nodes[i].l] = i; parent[nodes[i].r] = i; }
+    std::vector<int> touched(N, 0);   // the last pass (1-based) with a move at or below the node
+    // boxes from node a up to the root; stops where a box did not change (the boxes above are
+    // then the unions of their children's already)
+    auto refit = [&](int a) {
+      for (; a >= 0; a = parent[a]) {
+        const Box b = merged(nodes[nodes[a].l].box, nodes[nodes[a].r].box);
+        if (same(b, nodes[a].box)) break;
+        nodes[a].box = b;
+      }
+    };
+    typedef std::pair<double, int> Cand;   // induced cost, node: a total order, so the heap's pops are too
+    std::vector<Cand> heap;
+    std::vector<std::pair<double, int>> order;
+    order.reserve(N);
+    for (int pass = 1; pass <= kReinsertPasses; pass++) {
+      order.clear();
+      for (int i = 0; i < N; i++) {
+        const int p = parent[i];
+        if (i == root || p == root || p < 0) continue;
+        if (pass > 1) {
+          const int s = nodes[p].l == i ? nodes[p].r : nodes[p].l;
+          if (touched[i] < pass - 1 && touched[p] < pass - 1 && touched[s] < pass - 1 && touched[parent[p]] < pass - 1)
+            continue;
+        }
+        order.push_back({area(nodes[i].box), i});
+      }
+      std::stable_sort(order.begin(), order.end(),
+                       [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first > b.first; });
+      int moved = 0;
+      for (const auto& o : order) {
+        const int x = o.second, p = parent[x];
+        if (p == root) continue;   // an earlier move of this pass put it under the root
+        const int g = parent[p];
+        const bool x_left = nodes[p].l == x;
+        const int s = x_left ? nodes[p].r : nodes[p].l;
+        const Box xb = nodes[x].box;
+        const double ax = area(xb);
+        // detach x and p: s takes p's place
+        (nodes[g].l == p ? nodes[g].l : nodes[g].r) = s;
+        parent[s] = g;
+        refit(g);
+        // the old position (beside s) first; another one has to be strictly better
+        double best = area(merged(nodes[s].box, xb));
+        for (int a = g; a >= 0; a = parent[a]) best += area(merged(nodes[a].box, xb)) - area(nodes[a].box);
+        int best_y = s;
+        heap.clear();
+        heap.push_back({0.0, root});
+        while (!heap.empty()) {
+          std::pop_heap(heap.begin(), heap.end(), std::greater<Cand>());
+          const Cand c = heap.back();
+          heap.pop_back();
+          if (c.first + ax >= best) break;
+          const int y = c.second;
+          const double total = c.first + area(merged(nodes[y].box, xb));
+          if (total < best) { best = total; best_y = y; }
+          if (nodes[y].l < 0) continue;
+          const double ci = total - area(nodes[y].box);
+          if (ci + ax < best) {
+            heap.push_back({ci, nodes[y].l});
+            std::push_heap(heap.begin(), heap.end(), std::greater<Cand>());
+            heap.push_back({ci, nodes[y].r});
+            std::push_heap(heap.begin(), heap.end(), std::greater<Cand>());
+          }
+        }
+        const int y = best_y;
+        if (y == root) {
+          // the root keeps its id: p takes over the root's children, the root gets (p, x)
+          nodes[p].l = nodes[root].l;
+          nodes[p].r = nodes[root].r;
+          nodes[p].box = nodes[root].box;
+          parent[nodes[p].l] = p;
+          parent[nodes[p].r] = p;
+          nodes[root].l = p;
+          nodes[root].r = x;
+          parent[p] = root;
+          parent[x] = root;
+          refit(root);
+        } else {
+          const int q = parent[y];
+          (nodes[q].l == y ? nodes[q].l : nodes[q].r) = p;
+          parent[p] = q;
+          nodes[p].l = y == s && x_left ? x : y;   // unmoved: the children keep their sides
+          nodes[p].r = y == s && x_left ? y : x;
+          nodes[p].box = merged(nodes[y].box, xb);
+          parent[y] = p;
+          parent[x] = p;
+          refit(q);
+        }
+        if (y != s) {
+          moved++;
+          touched[x] = touched[s] = touched[y] = pass;
+          for (int a = g; a >= 0; a = parent[a]) touched[a] = pass;
+          for (int a = p; a >= 0; a = parent[a]) touched[a] = pass;
+        }
+      }
+      if (!moved) break;
+    }
+    // leaves in the new DFS order, depth
+    std::vector<int> lp;
+    lp.reserve(leaf_prims.size());
+    depth = 0;
+    std::vector<std::pair<int, int>> st{{root, 0}};
+    while (!st.empty()) {
+      const int id = st.back().first, d = st.back().second;
+      st.pop_back();
+      depth = std::max(depth, d);
+      Node& nd = nodes[id];
+      if (nd.l < 0) {
+        const int s0 = (int)lp.size();
+        for (int k = 0; k < nd.count; k++) lp.push_back(leaf_prims[nd.start + k]);
+        nd.start = s0;
+        continue;
+      }
+      st.push_back({nd.r, d + 1});
+      st.push_back({nd.l, d + 1});
+    }
+    leaf_prims.swap(lp);
+  }
 };
 
 float pad_down(double v, double ext) {
@@ -372,6 +521,9 @@ float i2f(int v) {
 }
 
 }  // namespace
+
+static int emit_device_tree(const bdpt_scene_desc* d, HostScene& out, std::string& err, const Builder& T, int root,
+                            const std::vector<int>& ref_pos, bool& too_deep);
 
 int build_host_scene(const bdpt_scene_desc* d, HostScene& out, std::string& err, bool pt, bool inf) {
   if (!d || d->nprim <= 0 || !d->prim_type || !d->prim_geom || !d->prim_mat) {
@@ -569,31 +721,49 @@ int build_host_scene(const bdpt_scene_desc* d, HostScene& out, std::string& err,
   std::vector<int> ref_pos(n);
   for (int k = 0; k < n; k++) ref_pos[R.leaf_prims[k]] = k;
   // the device's tree (BDPT_BVH=ref traverses the reference's own tree instead)
+  // BDPT_BVH=sah: the binned SAH tree as built top-down, without the reinsertion passes (A/B)
   const char* bvh_env = getenv("BDPT_BVH");
-  const bool use_ref = bvh_env && std::string(bvh_env) == "ref";
-  Builder Bs;
-  int root = ref_root;
-  if (!use_ref) {
-    SahBuilder S;
-    S.pb = &pb;
-    S.desc = d;
-    // diagnostics / A-B: leaf size and SAH termination of the device tree (no effect on results)
-    if (const char* e = getenv("BDPT_SAH_LEAF")) S.leaf_max = std::max(1, std::min(4, atoi(e)));
-    if (const char* e = getenv("BDPT_SAH_CT")) S.ct = atof(e);
-    if (const char* e = getenv("BDPT_SAH_BINS")) S.nb = std::max(2, std::min(SahBuilder::kMaxBins, atoi(e)));
-    // spatial splits (scenes of >= kSbvhMinPrims primitives): alpha and the reference budget
-    if (n >= kSbvhMinPrims) {
-      S.alpha = kSbvhAlpha;
-      S.budget = kSbvhBudget;
+  const std::string bvh_mode = bvh_env ? bvh_env : "";
+  const bool use_ref = bvh_mode == "ref";
+  bool reinsert = !use_ref && bvh_mode != "sah";
+  // spatial splits (scenes of >= kSbvhMinPrims primitives): alpha and the reference budget
+  double alpha = n >= kSbvhMinPrims ? kSbvhAlpha : 0.0, budget = n >= kSbvhMinPrims ? kSbvhBudget : 0.0;
+  if (const char* e = getenv("BDPT_SBVH")) alpha = n >= kSbvhMinPrims ? atof(e) : 0.0;
+  if (const char* e = getenv("BDPT_SBVH_BUDGET")) budget = atof(e);
+  // A tree too deep for the traversal stack is built again without the reinsertion passes, then
+  // without spatial splits: no scene fails that the plain SAH tree serves.
+  for (;;) {
+    Builder Bs;
+    int root = ref_root;
+    if (!use_ref) {
+      SahBuilder S;
+      S.pb = &pb;
+      S.desc = d;
+      // diagnostics / A-B: leaf size and SAH termination of the device tree (no effect on results)
+      if (const char* e = getenv("BDPT_SAH_LEAF")) S.leaf_max = std::max(1, std::min(4, atoi(e)));
+      if (const char* e = getenv("BDPT_SAH_CT")) S.ct = atof(e);
+      if (const char* e = getenv("BDPT_SAH_BINS")) S.nb = std::max(2, std::min(SahBuilder::kMaxBins, atoi(e)));
+      S.alpha = alpha;
+      S.budget = budget;
+      root = S.build_root(n);
+      if (reinsert) S.reinsert_optimise(root);
+      Bs.nodes = std::move(S.nodes);
+      Bs.leaf_prims = std::move(S.leaf_prims);
+      Bs.depth = S.depth;
     }
-    if (const char* e = getenv("BDPT_SBVH")) S.alpha = n >= kSbvhMinPrims ? atof(e) : 0.0;
-    if (const char* e = getenv("BDPT_SBVH_BUDGET")) S.budget = atof(e);
-    root = S.build_root(n);
-    Bs.nodes = std::move(S.nodes);
-    Bs.leaf_prims = std::move(S.leaf_prims);
-    Bs.depth = S.depth;
+    bool too_deep = false;
+    const int rc = emit_device_tree(d, out, err, use_ref ? R : Bs, root, ref_pos, too_deep);
+    if (!too_deep || use_ref) return rc;
+    if (reinsert) reinsert = false;
+    else if (alpha > 0) alpha = 0;
+    else return rc;
   }
-  Builder& T = use_ref ? R : Bs;
+}
+
+// Flattens the binary tree T for the device: the primitive records in T's DFS leaf order and the
+// 2- and 4-wide node arrays. too_deep: BDPT_E_UNSUPPORTED is the traversal stack's depth limit.
+static int emit_device_tree(const bdpt_scene_desc* d, HostScene& out, std::string& err, const Builder& T, int root,
+                            const std::vector<int>& ref_pos, bool& too_deep) {
   out.dev_depth = T.depth;
   out.dev_nodes = (int)T.nodes.size();
 
@@ -728,6 +898,7 @@ int build_host_scene(const bdpt_scene_desc* d, HostScene& out, std::string& err,
     B.depth = wdepth;
     if ((W - 1) * (wdepth + 1) + 2 > kStackMax) {
       err = "BVH deeper than the traversal stack";
+      too_deep = true;
       return BDPT_E_UNSUPPORTED;
     }
     bool wide_sph_leaf = false;

@@ -71,9 +71,11 @@ constexpr int kTopNodes = 1024;
 // object split leaves children overlapping by more than kSbvhAlpha x the root's surface area, up
 // to kSbvhBudget x n extra primitive references, in scenes of >= kSbvhMinPrims primitives (the
 // flat-list and all-in-LDS scenes stay unsplit). kSbvhAlpha 0 = off. Run-time A/B: BDPT_SBVH=alpha,
-// BDPT_SBVH_BUDGET=fraction.
+// BDPT_SBVH_BUDGET=fraction. Off by default since the reinsertion passes (SahBuilder::
+// reinsert_optimise): they gain more on the unsplit tree than on the split one;
+// BDPT_SBVH=1e-5 gives the split tree of before (the budget keeps its value for that).
 constexpr int kSbvhMinPrims = 256;
-constexpr double kSbvhAlpha = 1e-5;
+constexpr double kSbvhAlpha = 0;
 constexpr double kSbvhBudget = 0.3;
 
 // LM 3's flat list as one run of primitives: when the device tree's leaves, in DFS order, hold

@@ -5,7 +5,11 @@ visit order as the GPU), and its expected maximum over the 48 lanes that walk in
 wave-level iteration count of the node loop. Used to screen tree-building
 changes before a GPU run; results are checked bit-exact against oracle mode 2 at the same time.
 
-  python3 tools/step_hist.py [env KEY=VAL ...]     e.g. BDPT_COLLAPSE=sah
+Also prints the device tree's SAH cost (sum of the inner nodes' areas + 0.5 x primitives x area per
+leaf, over the root's area) and its primitive reference count (tests/native/tree_check.cpp).
+
+  python3 tools/step_hist.py [scene ...] [env KEY=VAL ...]     e.g. standin CBgems BDPT_BVH=sah
+scenes: standin, CBbunny, CBgems (default: all three)
 """
 import ctypes as C
 import os
@@ -16,9 +20,11 @@ import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(REPO, "bidirectional-pathtracing_amd"), os.path.join(REPO, "tests")]
+only = [a for a in sys.argv[1:] if "=" not in a]
 for kv in sys.argv[1:]:
-    k, v = kv.split("=", 1)
-    os.environ[k] = v
+    if "=" in kv:
+        k, v = kv.split("=", 1)
+        os.environ[k] = v
 import bdpt_amd as B  # noqa: E402
 from _util import MODE_C32, golden_scene, oracle_render  # noqa: E402
 
@@ -28,8 +34,15 @@ subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shar
                 "-I" + os.path.join(REPO, "include"), "-I" + CS, "-o", LIB,
                 os.path.join(REPO, "tests", "native", "core_cpu.cpp"), os.path.join(CS, "bdpt_scene.cpp")], check=True)
 lib = C.CDLL(LIB)
+TLIB = "/tmp/libtreecheck_stephist.so"
+subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I" + os.path.join(REPO, "include"),
+                "-I" + CS, "-o", TLIB, os.path.join(REPO, "tests", "native", "tree_check.cpp"),
+                os.path.join(CS, "bdpt_scene.cpp")], check=True)
+tlib = C.CDLL(TLIB)
 for name, W, H, spp, M, lm in [("standin", 192, 108, 2, 5, 2), ("CBbunny", 160, 120, 2, 5, 2),
                                ("CBgems", 192, 108, 2, 7, 0)]:
+    if only and name not in only:
+        continue
     if name == "standin":
         sc = B.load_dae(os.path.join(REPO, "scenes", "CBlucy_standin.dae"), W, H)
     elif name == "CBbunny":
@@ -39,6 +52,10 @@ for name, W, H, spp, M, lm in [("standin", 192, 108, 2, 5, 2), ("CBbunny", 160, 
     eye, light, st = np.zeros((H, W, 3)), np.zeros((H, W, 3)), np.zeros(8)
     pd = C.POINTER(C.c_double)
     d = sc.desc()
+    info, sah = (C.c_int * 8)(), C.c_double()
+    assert tlib.tree_check(C.byref(d), info, C.byref(sah)) == 0 and info[3] == 1
+    print(f"{name}: tree SAH {sah.value:.2f}, {info[2]} primitive references, {info[0]} binary nodes, depth {info[1]} "
+          f"(4-wide levels {info[5]})", flush=True)
     rc = lib.core_cpu_render(C.byref(d), W, H, spp, M, C.c_uint64(5489), 0, spp, None, 0, eye.ctypes.data_as(pd),
                              light.ctypes.data_as(pd), st.ctypes.data_as(pd), lm, 0)
     assert rc == 0
