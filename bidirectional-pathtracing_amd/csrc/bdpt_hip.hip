@@ -792,6 +792,14 @@ int bdpt_create(const bdpt_scene_desc* scene, const bdpt_params* params, void** 
       return BDPT_E_INVALID;
     }
   }
+  // the speculative loop of traverse<LM 0 / 2> reaches a leaf only out of a node step: started on a
+  // leaf reference it never ends, so the 4-wide tree's root must be a node (bdpt_scene.cpp emits a
+  // one-slot node around a leaf root)
+  if (c->hs.nprim > 0 && c->hs.bvh4.root < 0) {
+    g_err = "device tree: the 4-wide tree's root is a leaf reference (the 4-wide traversal needs a node)";
+    delete c;
+    return BDPT_E_UNSUPPORTED;
+  }
   c->ext = kernel_flavour(c->hs, p.russian_roulette != 0);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {

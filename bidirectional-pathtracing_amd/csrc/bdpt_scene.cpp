@@ -894,6 +894,14 @@ static int emit_device_tree(const bdpt_scene_desc* d, HostScene& out, std::strin
         for (int k = (int)ch.size() - 1; k >= 0; k--)
           if (T.nodes[ch[k]].l >= 0) st.push_back({ch[k], dd + 1});
       }
+    } else if (W == 4) {
+      // A root that is a leaf (one or two primitives): the 4-wide tree still starts at a node, the
+      // leaf in its slot 0 and three empty slots. The speculative loop of traverse<LM 0 / 2>
+      // (bdpt_bvh.h) reaches a leaf only out of a node step; started on a leaf reference it never
+      // ends. The 2-wide tree keeps its leaf root: the plain loop handles one.
+      order.push_back(root);
+      kids.push_back({root});
+      B.n_top = 1;
     }
     B.depth = wdepth;
     if ((W - 1) * (wdepth + 1) + 2 > kStackMax) {
@@ -953,7 +961,7 @@ static int emit_device_tree(const bdpt_scene_desc* d, HostScene& out, std::strin
         }
       }
     }
-    B.root = ref_of(root);
+    B.root = W == 4 && T.nodes[root].l < 0 ? 0 : ref_of(root);
     if (W == 2) {   // every leaf reference in DFS order: the flat traversal of tiny scenes (LM 3)
       out.leaf_refs.clear();
       std::vector<int> st{root};

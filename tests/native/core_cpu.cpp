@@ -9,6 +9,7 @@
 
 using namespace bdpt;
 
+#ifndef CORE_CPU_TRACE_ONLY   // (stack_probe's sanitizer build takes the ray queries alone: a third of the compile time)
 struct HostSink {
   std::vector<double>* light;
   int W;
@@ -205,6 +206,8 @@ extern "C" int core_cpu_dev_tree(const bdpt_scene_desc* d, int* depth, int* node
   return 0;
 }
 
+#endif   // CORE_CPU_TRACE_ONLY
+
 // Closest hits of the device traversal (lds_mode 0, 1 or 2) against a brute-force loop over every
 // primitive with the same tests and tie rule, for n rays with origins spread over the scene's box and
 // directions with exact zero (and -0) components: axis-aligned and in the coordinate planes (a zero
@@ -290,10 +293,11 @@ extern "C" int core_cpu_trace_check(const bdpt_scene_desc* d, int lds_mode, int 
 // bdpt_trace_rays (k_trace_rays) on the CPU: rays = n x (o, d, tmin, tmax); closest hit t and the
 // primitive's scene index (-1: none), or for any_hit whether anything lies in [tmin, tmax]
 template <int LM>
-static void trace_rays_lm(const HostScene& hs, const float* rays, int n, int any_hit, float* out_t, int* out_prim) {
+static void trace_rays_lm(const HostScene& hs, const float* rays, int n, int any_hit, float* out_t, int* out_prim,
+                          unsigned* visits = nullptr) {
   const SceneView S = trace_view<LM>(hs);
-  Counters c = {};
   for (int i = 0; i < n; i++) {
+    Counters c = {};
     const float* r = rays + 8 * (size_t)i;
     const f3 o = mk3(r[0], r[1], r[2]), d = mk3(r[3], r[4], r[5]);
     if (any_hit) {
@@ -306,6 +310,7 @@ static void trace_rays_lm(const HostScene& hs, const float* rays, int n, int any
       out_t[i] = ok ? h.t : INFINITY;
       out_prim[i] = ok ? hs.prim_ref[h.prim] : -1;
     }
+    if (visits) visits[i] = c.nodes;
   }
 }
 
@@ -317,6 +322,36 @@ extern "C" int core_cpu_trace_rays(const bdpt_scene_desc* d, int lds_mode, const
   if (lds_mode == 1) trace_rays_lm<1>(hs, rays, n, any_hit, out_t, out_prim);
   else if (lds_mode == 2) trace_rays_lm<2>(hs, rays, n, any_hit, out_t, out_prim);
   else trace_rays_lm<0>(hs, rays, n, any_hit, out_t, out_prim);
+  return 0;
+}
+
+// The same over one scene build for LDS modes 0, 1, 2 and both query kinds, with each ray's node
+// visits (Counters::nodes: a node step counts its W child slots): out_prim and visits hold n entries
+// per (mode, query) at ((2 * mode + any_hit) * n), info 5 per mode = W, the nodes and wide-node
+// levels of the tree that mode traverses, the traversal stack entries that tree needs, kStackMax
+// (tests/native/stack_probe.cpp)
+extern "C" int core_cpu_trace_visits(const bdpt_scene_desc* d, const float* rays, int n, int* out_prim,
+                                     unsigned* visits, int* info) {
+  HostScene hs;
+  std::string err;
+  if (build_host_scene(d, hs, err) != BDPT_OK) return -1;
+  std::vector<float> t(n);
+  for (int lm = 0; lm < 3; lm++) {
+    const int W = lm_width(lm);
+    const HostBvh& T = hs.tree(W);
+    int* f = info + 5 * lm;
+    f[0] = W;
+    f[1] = (int)(T.nodes.size() / ((size_t)4 * node_f4(W)));
+    f[2] = T.depth + 1;
+    f[3] = (W - 1) * (T.depth + 1) + 2;
+    f[4] = kStackMax;
+    for (int any = 0; any < 2; any++) {
+      const size_t at = (size_t)(2 * lm + any) * n;
+      if (lm == 1) trace_rays_lm<1>(hs, rays, n, any, t.data(), out_prim + at, visits + at);
+      else if (lm == 2) trace_rays_lm<2>(hs, rays, n, any, t.data(), out_prim + at, visits + at);
+      else trace_rays_lm<0>(hs, rays, n, any, t.data(), out_prim + at, visits + at);
+    }
+  }
   return 0;
 }
 

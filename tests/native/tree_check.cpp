@@ -90,7 +90,8 @@ bool walk(const HostScene& hs, int W, double* sah) {
       if (seen[it.node]) return false;   // a node reached twice: not a tree
       seen[it.node] = 1;
       const std::vector<Child> ch = children(B, W, it.node);
-      if (ch.size() < 2) return false;
+      // a node has two children or more; the 4-wide root around a leaf root has the one leaf
+      if (ch.size() < 2 && !(W == 4 && !it.bounded && ch.size() == 1 && ch[0].ref < 0)) return false;
       FBox un = ch[0].box;
       for (const Child& c : ch) {
         for (int a = 0; a < 3; a++) {
@@ -132,6 +133,8 @@ extern "C" int tree_check(const bdpt_scene_desc* d, int* info, double* sah) {
   if (rc != BDPT_OK) return rc;
   bool ok = walk(hs, 2, sah);
   ok = walk(hs, 4, nullptr) && ok;
+  // the 4-wide tree's root is a node: its speculative traversal never ends on a leaf reference
+  if (hs.nprim > 0 && hs.bvh4.root < 0) ok = false;
   std::vector<char> used(hs.nprim, 0);
   for (int32_t p : hs.prim_ref) {
     if (p < 0 || p >= hs.nprim) { ok = false; continue; }

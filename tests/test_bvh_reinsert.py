@@ -178,11 +178,12 @@ def _degenerate(kind):
         # normal and material whichever copy is hit
         return (_with_prims(base, np.repeat(tris[:1], 64, axis=0), np.repeat(mats[:1], 64)),
                 _with_prims(base, tris[:1], mats[:1]), (0, 1))
-    # A tree whose root is a leaf (1 or 2 triangles) is rendered as the product renders it, from
-    # the flat list or the binary tree: the 4-wide traversal is never given such a tree (and does
-    # not terminate on one in the CPU build).
+    # A tree whose root is a leaf (1 or 2 triangles): the 4-wide tree wraps the leaf in a one-slot
+    # root node (emit_device_tree), so every mode renders it: the 4-wide tree with and without its
+    # treelet (0, 2), the binary tree (1) and the flat list (3). Started on a bare leaf reference
+    # the 4-wide traversal did not terminate; bdpt_trace_rays and BDPT_LDS_MODE=0 / 2 reach it.
     sc = _with_prims(base, tris[:int(kind)], mats[:int(kind)])
-    return sc, sc, (1, 3) if int(kind) < 3 else (0, 1, 3)
+    return sc, sc, (0, 1, 2, 3) if int(kind) < 3 else (0, 1, 3)
 
 
 @pytest.mark.parametrize("kind", ["1", "2", "3", "same64", "CBspheres"])
