@@ -337,6 +337,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                   C.POINTER(C.POINTER(C.c_float))]
     lib.bdpt_exr_free.argtypes = [C.POINTER(C.c_float)]
     lib.bdpt_exr_free.restype = None
+    lib.bdpt_debug_launch_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     lib.bdpt_reduce_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]
     lib.bdpt_reduce_frames.argtypes = [C.c_void_p, C.c_int32]
     lib.bdpt_reduce_ranks.argtypes = [C.c_void_p]
@@ -452,6 +453,13 @@ class BidirectionalPathTracer:
         s = Stats()
         _check(self.lib.bdpt_get_stats(self.ctx, C.byref(s)), self.lib)
         return s
+
+    def launch_plan(self) -> dict:
+        """The last launch's plan as the host chose it (bdpt_debug_launch_plan): lm, lstack_on, ntop,
+        lds_bytes, grid, spl, nitems, staged (materials / lights copied to LDS); -1 = not applicable."""
+        out = (C.c_int32 * 8)()
+        _check(self.lib.bdpt_debug_launch_plan(self.ctx, out), self.lib)
+        return dict(zip(("lm", "lstack_on", "ntop", "lds_bytes", "grid", "spl", "nitems", "staged"), list(out)))
 
     def trace_rays(self, rays: np.ndarray, any_hit: bool = False):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)

@@ -64,6 +64,10 @@ struct Ctx {
   // BDPT_XCD_GROUPS): -1 = not set.
   int env_lds_mode = -1, env_ntop_max = -1, block_major = 1, xcd = 0;
   int last_lm = -1;            // LDS mode of the last BDPT / PathTracer launch
+  // The rest of the last launch's plan (bdpt_debug_launch_plan): {lstack_on, ntop, dynamic LDS bytes,
+  // grid blocks, samples per lane, work items, materials / lights staged in LDS}; -1 = none yet,
+  // and for what a PathTracer launch does not have (lstack_on, spl, staged).
+  int last_plan[7] = {-1, -1, -1, -1, -1, -1, -1};
   int maxv = 5;
   int ncu = 256;
   size_t npix = 0;

@@ -627,7 +627,11 @@ int launch_persistent(Ctx* c, K kernel, const char* name, size_t lds, const KP& 
   HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, lds));
   if (per_cu <= 0) { g_err = std::string(name) + " cannot be resident (LDS/VGPR budget)"; return BDPT_E_DEVICE; }
   long long grid = std::min<long long>((long long)per_cu * c->ncu, (items + kWavesPerBlock - 1) / kWavesPerBlock);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)std::max(1LL, grid)), dim3(kBlock), lds, c->stream, kp);
+  grid = std::max(1LL, grid);
+  c->last_plan[2] = (int)lds;
+  c->last_plan[3] = (int)grid;
+  c->last_plan[5] = (int)items;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kBlock), lds, c->stream, kp);
   HIPCHK(hipGetLastError());
   return BDPT_OK;
 }
@@ -673,10 +677,18 @@ int pick_lm(Ctx* c, KParams& kp, size_t* lds) {
   return lm;
 }
 
+// Whether k_bdpt_sample copies the materials and lights to its static LDS arrays: the predicate
+// stage_scene evaluates, on the host for bdpt_debug_launch_plan.
+bool mats_lights_staged(const KParams& kp) { return kp.nmat <= kLdsMats && kp.S.nlights <= kLdsLights; }
+
 template <int MAXV, bool STATS, int EXT>
 int launch_lm(Ctx* c, KParams& kp) {
   size_t lds = 0;
   const int lm = pick_lm(c, kp, &lds);
+  c->last_plan[0] = kp.lstack_on;
+  c->last_plan[1] = kp.S.ntop;
+  c->last_plan[4] = kp.spl;
+  c->last_plan[6] = mats_lights_staged(kp) ? 1 : 0;
   if (lm == 3) return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 3, EXT>, "k_bdpt_sample", lds, kp, kp.nitems);
   if (lm == 1) return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 1, EXT>, "k_bdpt_sample", lds, kp, kp.nitems);
   if (lm == 2) return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 2, EXT>, "k_bdpt_sample", lds, kp, kp.nitems);
@@ -697,6 +709,8 @@ int launch_pt(Ctx* c, PtKParams& kp) {
   const int lm = pick_lds_copy(c, kp, lds_max, lds_max, &flat, &full);
   kp.n_geom4 = (int)(c->hs.geom.size() / 4);
   const size_t lds = lds_copy_bytes(lm, kp.S, flat, full);
+  c->last_plan[0] = c->last_plan[4] = c->last_plan[6] = -1;   // k_pt: no stack slots, chunks or material copy
+  c->last_plan[1] = kp.S.ntop;
   if (lm == 3) return launch_persistent(c, k_pt<STATS, 3>, "k_pt", lds, kp, kp.nblocks);
   if (lm == 1) return launch_persistent(c, k_pt<STATS, 1>, "k_pt", lds, kp, kp.nblocks);
   if (lm == 2) return launch_persistent(c, k_pt<STATS, 2>, "k_pt", lds, kp, kp.nblocks);
@@ -1141,6 +1155,15 @@ int bdpt_debug_counters(void* ctx, uint64_t* out16) {
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipMemcpy(out16, c->d_stats + 16, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return BDPT_OK;
+}
+
+int bdpt_debug_launch_plan(void* ctx, int32_t* out8) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c || !out8) { g_err = "null argument"; return BDPT_E_INVALID; }
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  out8[0] = c->last_lm;
+  for (int k = 0; k < 7; k++) out8[1 + k] = c->last_plan[k];
   return BDPT_OK;
 }
 

@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define BDPT_ABI_VERSION 9
+#define BDPT_ABI_VERSION 10
 
 enum bdpt_status {
   BDPT_OK = 0,
@@ -288,6 +288,13 @@ int bdpt_debug_counters(void* ctx, uint64_t* out16);
  * shading, walk iterations, connection evaluations, connection-ray flushes) out16[2k] = wave-level
  * iterations and out16[2k+1] = active lanes summed over them. Sync. Zero in product builds. */
 int bdpt_debug_lane_counters(void* ctx, uint64_t* out16);
+/* Diagnostic hook (ABI v10): the plan of the ctx's last launch, as the host chose it — out8 = {LDS
+ * mode (bdpt_stats.lds_mode), 1 if the traversal stacks have their LDS overflow slots, treelet
+ * nodes staged in LDS (LDS mode 2, else 0), dynamic LDS bytes per block, blocks launched, samples
+ * per lane and work item, work items (PathTracer: pixel blocks), 1 if the kernel copies the
+ * materials and lights to LDS (0: it reads them from global memory)}. -1: no launch yet, or not
+ * applicable to the PathTracer's kernel. Touches no device. */
+int bdpt_debug_launch_plan(void* ctx, int32_t* out8);
 
 /* Host-side COLLADA loader: the reference CLI's scene path (ColladaParser::load,
  * collada.cpp:129-941, + Application::load, application.cpp:228-304). width/height > 0 apply

@@ -1,6 +1,7 @@
 // tests/native/core_cpu.cpp — TEST ONLY. Compiles the device-side pipeline (bdpt_core.h) and the
 // host scene preparation (bdpt_scene.cpp) with g++ so the per-sample arithmetic can be checked
 // against the oracle on the CPU before it runs on the GPU. Never linked into the product.
+#include <cmath>
 #include <cstdio>
 #include <vector>
 
@@ -10,18 +11,74 @@
 using namespace bdpt;
 
 #ifndef CORE_CPU_TRACE_ONLY   // (stack_probe's sanitizer build takes the ray queries alone: a third of the compile time)
-struct HostSink {
-  std::vector<double>* light;
-  int W;
-  void splat(int x, int y, f3 v) {
-    size_t k = 3 * ((size_t)x + (size_t)y * W);
-    (*light)[k] += v.x; (*light)[k + 1] += v.y; (*light)[k + 2] += v.z;
+// A flat record of fp32 addends: entry k is (pix[k] = x + y * W, rgb[3k..3k+2]). n counts every
+// entry offered; only the first cap are stored.
+struct AddendRec {
+  int* pix;
+  float* rgb;
+  long long cap, n;
+  float vmin;   // the smallest component offered
+  void put(int p, f3 v) {
+    vmin = fminf(vmin, fminf(v.x, fminf(v.y, v.z)));
+    if (pix && n < cap) { pix[n] = p; rgb[3 * n] = v.x; rgb[3 * n + 1] = v.y; rgb[3 * n + 2] = v.z; }
+    n++;
   }
 };
 
+// What core_cpu_render_rec records beside the frames (tests/_pixelbound.py): the light image's
+// splat count per pixel, and on request every splat, every eye-image addend (one connection's
+// value, before the 1 / spp factor) and every per-sample eye value (after it).
+struct Recorder {
+  int* nsplat;   // W * H
+  AddendRec splats, eye_addends, eye_samples;
+};
+
+struct HostSink {
+  std::vector<double>* light;
+  int W;
+  Recorder* rec = nullptr;
+  void splat(int x, int y, f3 v) {
+    size_t k = 3 * ((size_t)x + (size_t)y * W);
+    (*light)[k] += v.x; (*light)[k + 1] += v.y; (*light)[k + 2] += v.z;
+    if (rec) {
+      rec->nsplat[x + y * W]++;
+      rec->splats.put(x + y * W, v);
+    }
+  }
+};
+
+// render_sample (bdpt_paths.h), statement for statement, with every eye-image addend recorded
+// (tests/test_pixel_bounds.py holds the two bit-equal).
+template <int MAXV, int LM, int EXT>
+static f3 sample_recorded(const SceneView& S, const SampleParams& sp, Paths<MAXV>& P, Counters& cnt, int x, int y,
+                          uint32_t sample, HostSink& sink) {
+  Rng g;
+  prepare_sample<MAXV, LM, EXT>(S, sp, P, cnt, g, x, y, sample);
+  f3 eye_sum = splat3(0);
+  for (int i = 1; i < P.nE; i++) {
+    for (int j = 0; j < P.nL; j++) {
+      Conn cn;
+      int kind = make_conn<EXT>(S, sp, PathsInRegs<MAXV, EXT>(P), g, i, j, cn);
+      if (kind == CONN_DIRECT) {
+        eye_sum = add(eye_sum, cn.val);
+        sink.rec->eye_addends.put(x + y * sp.W, cn.val);
+      } else if (kind == CONN_RAY) {
+        if (trace_any<LM>(S, cn.o, cn.d, BDPT_EPS_F, cn.tmax, cnt)) continue;
+        if (cn.splat >= 0) sink.splat(cn.splat % sp.W, cn.splat / sp.W, cn.val);
+        else {
+          eye_sum = add(eye_sum, cn.val);
+          sink.rec->eye_addends.put(x + y * sp.W, cn.val);
+        }
+      }
+    }
+  }
+  return eye_sum;
+}
+
 template <int MAXV, int LM, bool EXT>
 static int run(const HostScene& hs, int W, int H, int spp, int M, uint64_t seed, int s0, int count,
-               const int* pixels, int npix, double* eye, double* light, double* stats, int rr) {
+               const int* pixels, int npix, double* eye, double* light, double* stats, int rr,
+               Recorder* rec = nullptr) {
   SceneView S;
   const HostBvh& T = hs.tree(lm_width(LM));
   S.nodes = (const float4*)T.nodes.data();
@@ -60,7 +117,7 @@ static int run(const HostScene& hs, int W, int H, int spp, int M, uint64_t seed,
   sp.W = W; sp.H = H; sp.spp = spp; sp.max_depth = M; sp.seed = seed;
   sp.rr = rr;
   std::vector<double> lb((size_t)W * H * 3, 0.0);
-  HostSink sink{&lb, W};
+  HostSink sink{&lb, W, rec};
   Counters cnt = {0, 0, 0, 0, 0, 0};
   Paths<MAXV>* P = new Paths<MAXV>();
   float inv = 1.0f / (float)spp;
@@ -68,8 +125,10 @@ static int run(const HostScene& hs, int W, int H, int spp, int M, uint64_t seed,
   for (int q = 0; q < total; q++) {
     int x = pixels ? pixels[2 * q] : q % W, y = pixels ? pixels[2 * q + 1] : q / W;
     for (int s = s0; s < s0 + count; s++) {
-      f3 v = render_sample<MAXV, LM, EXT>(S, sp, *P, cnt, x, y, (uint32_t)s, sink);
+      f3 v = rec ? sample_recorded<MAXV, LM, EXT>(S, sp, *P, cnt, x, y, (uint32_t)s, sink)
+                 : render_sample<MAXV, LM, EXT>(S, sp, *P, cnt, x, y, (uint32_t)s, sink);
       size_t k = 3 * ((size_t)x + (size_t)y * W);
+      if (rec) rec->eye_samples.put(x + y * W, mk3(v.x * inv, v.y * inv, v.z * inv));
       eye[k] += (double)(v.x * inv); eye[k + 1] += (double)(v.y * inv); eye[k + 2] += (double)(v.z * inv);
     }
   }
@@ -84,28 +143,30 @@ static int run(const HostScene& hs, int W, int H, int spp, int M, uint64_t seed,
 
 template <int LM, bool EXT>
 static int render_maxv(const HostScene& hs, int W, int H, int spp, int M, uint64_t seed, int s0, int count,
-                       const int* pixels, int npix, double* eye, double* light, double* stats, int rr) {
+                       const int* pixels, int npix, double* eye, double* light, double* stats, int rr,
+                       Recorder* rec) {
   int need = M < 1 ? 1 : M;
-  if (need <= 5) return run<5, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
-  if (need <= 8) return run<8, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
-  if (need <= 16) return run<16, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
-  if (need <= 32) return run<32, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
-  if (need <= 62) return run<62, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
-  if (need <= 126) return run<126, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
+  if (need <= 5) return run<5, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
+  if (need <= 8) return run<8, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
+  if (need <= 16) return run<16, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
+  if (need <= 32) return run<32, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
+  if (need <= 62) return run<62, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
+  if (need <= 126) return run<126, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
   return BDPT_E_UNSUPPORTED;
 }
 
 template <int LM>
 static int render_lm(const bdpt_scene_desc* d, int W, int H, int spp, int M, uint64_t seed, int s0,
-                     int count, const int* pixels, int npix, double* eye, double* light, double* stats, int rr) {
+                     int count, const int* pixels, int npix, double* eye, double* light, double* stats, int rr,
+                     Recorder* rec = nullptr) {
   HostScene hs;
   std::string err;
   int rc = build_host_scene(d, hs, err);
   if (rc) { fprintf(stderr, "core_cpu: %s\n", err.c_str()); return rc; }
   // the kernel selection of bdpt_create: EXT kernels for an environment light or roulette
   if (hs.env_light >= 0 || rr)
-    return render_maxv<LM, true>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
-  return render_maxv<LM, false>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
+    return render_maxv<LM, true>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
+  return render_maxv<LM, false>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
 }
 
 // lds_mode 0: the HBM tree (lm_width(0) children per node); 1: the LDS-mode tree (lm_width(1));
@@ -117,6 +178,50 @@ extern "C" int core_cpu_render(const bdpt_scene_desc* d, int W, int H, int spp, 
   if (lds_mode == 2) return render_lm<2>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
   if (lds_mode == 3) return render_lm<3>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
   return render_lm<0>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
+}
+
+// core_cpu_render with the addends on record (tests/_pixelbound.py; small frames): nsplat = W * H
+// ints, the light image's splats per pixel (added to). Each of the three records is optional (null
+// pix: only counted): splats, eye-image addends (a connection's value before the 1 / spp factor) and
+// per-sample eye values (after it), as (pix = x + y * W, r, g, b) with room for cap[k] entries;
+// n_out[k] = entries offered (> cap[k]: the record is cut short), vmin[k] = the smallest component
+// among them (+inf for none): no addend may be negative.
+extern "C" int core_cpu_render_rec(const bdpt_scene_desc* d, int W, int H, int spp, int M, uint64_t seed, int s0,
+                                   int count, const int* pixels, int npix, double* eye, double* light, double* stats,
+                                   int lds_mode, int rr, int* nsplat, int* splat_pix, float* splat_rgb,
+                                   int* addend_pix, float* addend_rgb, int* sample_pix, float* sample_rgb,
+                                   const long long* cap, long long* n_out, float* vmin) {
+  Recorder rec = {nsplat, {splat_pix, splat_rgb, cap[0], 0, INFINITY}, {addend_pix, addend_rgb, cap[1], 0, INFINITY},
+                  {sample_pix, sample_rgb, cap[2], 0, INFINITY}};
+  int rc;
+  if (lds_mode == 1) rc = render_lm<1>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, &rec);
+  else if (lds_mode == 2) rc = render_lm<2>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, &rec);
+  else if (lds_mode == 3) rc = render_lm<3>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, &rec);
+  else rc = render_lm<0>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, &rec);
+  n_out[0] = rec.splats.n; n_out[1] = rec.eye_addends.n; n_out[2] = rec.eye_samples.n;
+  vmin[0] = rec.splats.vmin; vmin[1] = rec.eye_addends.vmin; vmin[2] = rec.eye_samples.vmin;
+  return rc;
+}
+
+// What the LDS plan of a launch is chosen from (bdpt_hip.hip pick_lds_copy / pick_lm), from the same
+// build_host_scene: out8 = {primitive records, bytes of the whole-scene copy (binary tree + geometry),
+// bytes of the flat-list copy, the 4-wide tree's BFS treelet candidates (n_top), bytes of one 4-wide
+// node, materials, lights, the flat list's length or 0}. infinite_lights: bdpt_params.infinite_lights.
+extern "C" int core_cpu_lds_facts(const bdpt_scene_desc* d, int infinite_lights, int* out8) {
+  HostScene hs;
+  std::string err;
+  int rc = build_host_scene(d, hs, err, false, infinite_lights != 0);
+  if (rc) return rc;
+  out8[0] = hs.nprim;
+  out8[1] = (int)((hs.tree(lm_width(1)).nodes.size() + hs.geom.size()) * sizeof(float));
+  out8[2] = (int)(2 * hs.geom.size() * sizeof(float) + (hs.leaf_refs.size() + 3) / 4 * 16);
+  out8[3] = hs.tree(lm_width(2)).n_top;
+  out8[4] = node_bytes(lm_width(2));
+  out8[5] = (int)hs.mats.size();
+  out8[6] = (int)hs.lights.size();
+  uint32_t sph = 0;
+  out8[7] = flat_prims(hs, &sph);
+  return 0;
 }
 
 extern "C" int core_cpu_scene_info(const bdpt_scene_desc* d, int* depth, int* ref_nodes, int* prim_ref) {

@@ -17,10 +17,15 @@ namespace {
 struct HostSink {
   std::vector<double>* light;
   int W;
+  int* nsplat = nullptr;   // the light image's splats per pixel (core_cpu_inf_render_counts)
+  float* vmin = nullptr;   // the smallest component of any addend so far
   void splat(int x, int y, f3 v) {
     size_t k = 3 * ((size_t)x + (size_t)y * W);
     (*light)[k] += v.x; (*light)[k + 1] += v.y; (*light)[k + 2] += v.z;
+    if (nsplat) nsplat[x + y * W]++;
+    note(v);
   }
+  void note(f3 v) { if (vmin) *vmin = fminf(*vmin, fminf(v.x, fminf(v.y, v.z))); }
 };
 
 template <int LM>
@@ -67,6 +72,8 @@ struct Job {
   const int* pixels;
   int npix;
   double *eye, *light, *stats;
+  int* nsplat = nullptr;   // with vmin: one thread only
+  float* vmin = nullptr;
 };
 
 // render_sample (bdpt_paths.h) with the s = 0 contributions counted: direct[0] = how many (i, 0)
@@ -83,12 +90,13 @@ f3 sample_counted(const SceneView& S, const SampleParams& sp, Paths<MAXV>& P, Co
       int kind = make_conn<EXT>(S, sp, PathsInRegs<MAXV, EXT>(P), g, i, j, cn);
       if (kind == CONN_DIRECT) {
         eye_sum = add(eye_sum, cn.val);
+        sink.note(cn.val);
         direct[0] += 1;
         direct[1] += (double)fabsf(cn.val.x) + (double)fabsf(cn.val.y) + (double)fabsf(cn.val.z);
       } else if (kind == CONN_RAY) {
         if (trace_any<LM>(S, cn.o, cn.d, BDPT_EPS_F, cn.tmax, cnt)) continue;
         if (cn.splat >= 0) sink.splat(cn.splat % sp.W, cn.splat / sp.W, cn.val);
-        else eye_sum = add(eye_sum, cn.val);
+        else { eye_sum = add(eye_sum, cn.val); sink.note(cn.val); }
       }
     }
   }
@@ -111,7 +119,7 @@ int run(const HostScene& hs, const Job& J) {
   std::vector<Counters> cnts(nt);
   std::vector<double> direct(2 * (size_t)nt, 0.0);
   auto work = [&](int t) {
-    HostSink sink{&lb[t], J.W};
+    HostSink sink{&lb[t], J.W, J.nsplat, J.vmin};
     Counters cnt = {0, 0, 0, 0, 0, 0};
     Paths<MAXV>* P = new Paths<MAXV>();
     for (int q = (int)((long long)total * t / nt); q < (int)((long long)total * (t + 1) / nt); q++) {
@@ -185,6 +193,23 @@ extern "C" int core_cpu_inf_render(const bdpt_scene_desc* d, int W, int H, int s
   Job J;
   J.W = W; J.H = H; J.spp = spp; J.M = M; J.s0 = s0; J.count = count; J.rr = rr; J.threads = threads;
   J.seed = seed; J.pixels = pixels; J.npix = npix; J.eye = eye; J.light = light; J.stats = stats;
+  if (lds_mode == 1) return render_lm<1>(d, J, infinite_lights);
+  if (lds_mode == 2) return render_lm<2>(d, J, infinite_lights);
+  if (lds_mode == 3) return render_lm<3>(d, J, infinite_lights);
+  return render_lm<0>(d, J, infinite_lights);
+}
+
+// The same on one thread, with the light image's splat count per pixel added to nsplat (W * H) and
+// *vmin lowered to the smallest component of any eye or light addend (tests/_pixelbound.py: the
+// addend counts of the per-pixel bound, and that no addend is negative).
+extern "C" int core_cpu_inf_render_counts(const bdpt_scene_desc* d, int W, int H, int spp, int M, uint64_t seed,
+                                          int s0, int count, const int* pixels, int npix, double* eye, double* light,
+                                          double* stats, int lds_mode, int rr, int infinite_lights, int* nsplat,
+                                          float* vmin) {
+  Job J;
+  J.W = W; J.H = H; J.spp = spp; J.M = M; J.s0 = s0; J.count = count; J.rr = rr; J.threads = 1;
+  J.seed = seed; J.pixels = pixels; J.npix = npix; J.eye = eye; J.light = light; J.stats = stats;
+  J.nsplat = nsplat; J.vmin = vmin;
   if (lds_mode == 1) return render_lm<1>(d, J, infinite_lights);
   if (lds_mode == 2) return render_lm<2>(d, J, infinite_lights);
   if (lds_mode == 3) return render_lm<3>(d, J, infinite_lights);

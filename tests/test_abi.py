@@ -31,7 +31,7 @@ def test_library_exports_every_declared_function():
 
 
 def test_abi_version():
-    assert B.load_library().bdpt_abi_version() == 9   # v2: envmap + RR; v3: integrator; v4: LDS stats; v5: camera settings; v6: env-table stats; v7: camera lens settings; v8: frame rectangles; v9: RCCL frame reduce
+    assert B.load_library().bdpt_abi_version() == 10   # v2: envmap + RR; v3: integrator; v4: LDS stats; v5: camera settings; v6: env-table stats; v7: camera lens settings; v8: frame rectangles; v9: RCCL frame reduce; v10: launch-plan diagnostics
 
 
 def test_frame_reduce_loads_rccl_and_validates_arguments():
@@ -53,6 +53,9 @@ def test_frame_reduce_loads_rccl_and_validates_arguments():
 def test_null_arguments_rejected():
     lib = B.load_library()
     assert lib.bdpt_create(None, None, None) == -1
+    assert b"null" in lib.bdpt_last_error()
+    out = (C.c_int32 * 8)()
+    assert lib.bdpt_debug_launch_plan(None, out) == B.BDPT_E_INVALID   # the diagnostics touch no device
     assert b"null" in lib.bdpt_last_error()
 
 

@@ -34,6 +34,9 @@ def _gpu_render(sc, W, H, S, M, seed=5489, tiles=(), ranges=None, spl=0, stats=F
                for k, v in (("sample", B.FRAME_SAMPLE), ("eye", B.FRAME_EYE),
                             ("light", B.FRAME_LIGHT))}
         out["stats"] = pt.stats()
+        # for the per-pixel eye bound: samples rendered per pixel (whole-frame renders only) and the depth
+        out["samples"] = None if tiles else sum(b - a for a, b in ranges)
+        out["max_depth"] = M
         return out
     finally:
         pt.close()
@@ -41,6 +44,14 @@ def _gpu_render(sc, W, H, S, M, seed=5489, tiles=(), ranges=None, spl=0, stats=F
 
 def _rmse(a, b):
     return float(np.sqrt(np.mean((a - b) ** 2)))
+
+
+def _check_eye_bound(g, eye, label):
+    """Every pixel of a whole-frame render's eye image within the derived fp32-reordering bound of the
+    oracle's (tests/_pixelbound.py; the light image's bound needs the CPU build's splat counts:
+    tests/test_gpu_pixel_bounds.py). No pixel may be outside."""
+    from _pixelbound import check_eye
+    check_eye(g["eye"], eye, g["samples"], g["max_depth"], label)
 
 
 @pytest.mark.parametrize("pipe", PIPES)
@@ -68,6 +79,7 @@ def test_parity_vs_oracle(name, W, H, S, M, pipe):
     print(f"{name} {W}x{H} s{S} m{M}: rmse sample {r:.3e} eye {re:.3e} light {rl:.3e} "
           f"mean gpu {g['sample'].mean():.6f} oracle {samp.mean():.6f}")
     assert r < RMSE_TOL and re < RMSE_TOL and rl < RMSE_TOL
+    _check_eye_bound(g, eye, f"{name} {W}x{H} s{S} m{M}")
 
 
 @pytest.mark.parametrize("lds", [None, 0])
@@ -333,6 +345,7 @@ def _check_frames(g, ref, label):
     print(f"{label}: rmse sample {r:.3e} eye {re_:.3e} light {rl:.3e} mean gpu {g['sample'].mean():.6f} "
           f"oracle {samp.mean():.6f}")
     assert r < RMSE_TOL and re_ < RMSE_TOL and rl < RMSE_TOL
+    _check_eye_bound(g, eye, label)
 
 
 def test_standin_c3_frame_default_mode():
