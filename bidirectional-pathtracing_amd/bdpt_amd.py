@@ -366,6 +366,7 @@ class BidirectionalPathTracer:
                  seed: int = 5489, device: int = 0, samples_per_lane: int = 0,
                  collect_stats: bool = False, pipeline: int = PIPELINE_AUTO,
                  russian_roulette: bool = False, infinite_lights: bool = False,
+                 lens_radius: float = 0.0, focal_distance: float = 4.7,
                  _pt: Optional[dict] = None):
         self.lib = load_library()
         self.scene = scene
@@ -378,6 +379,8 @@ class BidirectionalPathTracer:
         p.russian_roulette = 1 if russian_roulette else 0
         # ambient (hemisphere) and directional lights under BDPT; off: rejected
         p.infinite_lights = 1 if infinite_lights else 0
+        # the thin lens under BDPT: lens_radius > 0; 0 is the pinhole
+        p.lens_radius, p.focal_distance = lens_radius, focal_distance
         if _pt is not None:
             p.integrator = INTEGRATOR_PT
             p.ns_area_light = _pt["ns_area_light"]

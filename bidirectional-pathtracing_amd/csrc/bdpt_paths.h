@@ -38,8 +38,9 @@ struct LightSample {
 // probability of a connectable vertex) as a 13th dword. The private segment is lane-interleaved
 // per dword, so the dwords a kernel never touches cost no traffic.
 // EXT is the kernel flavour: 0 reference-only; 1 environment map and / or roulette (§9); 2 the
-// same plus hemisphere and directional lights (§9a). Code written `EXT ? ... : ...` serves 1 and 2;
-// what only flavour 2 has is behind `EXT >= 2`, so flavours 0 and 1 compile to what they were.
+// same plus hemisphere and directional lights (§9a); 3 flavour 2 plus the thin-lens camera (§9b).
+// Code written `EXT ? ... : ...` serves 1, 2 and 3; what flavour 2 adds is behind `EXT >= 2` and
+// what the lens adds behind `EXT >= 3`, so the lower flavours compile to what they were.
 struct VtxS {
   f3 pos;
   float fwd;
@@ -92,7 +93,10 @@ struct SampleParams {
   int W, H, spp, max_depth;
   uint64_t seed;
   int rr;   // Russian roulette (bdpt_params.russian_roulette; honoured by EXT kernels only)
+  float focal;   // the thin lens' focal distance (§9b; read by EXT = 3 only). It fills what was the
+                 // struct's tail padding, so no kernel argument moves
 };
+static_assert(sizeof(SampleParams) == 32, "SampleParams: the focal distance takes the tail padding");
 
 // Power-heuristic sums in Horner form. Along a subpath walked from the connection endpoint
 // inward, the reference accumulates ratio_k = f_end * ... * f_k and adds ratio_k^2 when neither
@@ -260,6 +264,70 @@ BDPT_HD EyeSample camera_sample(const DCam& c, int W, int H, f3 p) {
   e.y = (fy > -1.0f && fy < (float)H) ? (int)fy : -1;
   e.alpha = divs(splat3(1.0f / denom), 1.0f);
   e.pos = cam;
+  e.zh = zaxis(e.n);
+  return e;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The thin lens (Camera::generate_ray_for_thin_lens, camera_lens.cpp:22-43), EXT = 3.
+// Sub-streams of the lens uniforms: the walk's lens point, and one per camera connection (1, j).
+// (0: eye walk, 1: light sample + walk, 2 + i: the fresh light sample of (i, 1), i <= 127.)
+enum : uint32_t { RNG_LENS_WALK = 0x100u, RNG_LENS_CONN = 0x200u };
+BDPT_HD f3 cam_to_world(const DCam& c, f3 v) {
+  return add(add(smul(v.x, mk3(c.c2w[0], c.c2w[1], c.c2w[2])), smul(v.y, mk3(c.c2w[3], c.c2w[4], c.c2w[5]))),
+             smul(v.z, mk3(c.c2w[6], c.c2w[7], c.c2w[8])));
+}
+// pLens = r sqrt(u1) (cos 2 pi u2, sin 2 pi u2, 0) in camera space
+BDPT_HD f3 lens_plens(const DCam& c, float u1, float u2) {
+  const float r = c.lens_r * sqrtf(u1);
+  float cs, sn;
+  cos_sin_2pi(u2, &cs, &sn);
+  return mk3(r * cs, r * sn, 0.0f);
+}
+// The lens point of sub-stream `stream` of g's pixel-sample, in camera space. g is taken by value:
+// Philox is counter-based, so the point is recomputed wherever it is needed and the caller's stream
+// position stays where it was.
+BDPT_HD f3 lens_draw(const DCam& c, Rng g, uint32_t stream) {
+  rng_stream(g, stream);
+  const float u1 = rng_next(g);
+  const float u2 = rng_next(g);
+  return lens_plens(c, u1, u2);
+}
+BDPT_HD f3 lens_world(const DCam& c, f3 pl) { return add(mk3(c.pos[0], c.pos[1], c.pos[2]), cam_to_world(c, pl)); }
+// The eye ray through raster position (x, y) in [0, 1]^2 from lens point pl: toward the point
+// pFocus = ((2x - 1) tanh, (2y - 1) tanv, -1) F of the focal plane. The direction pFocus - pLens is
+// formed divided by F, as camera_dir's vector minus pLens / F: the same direction, and one that
+// turns into the pinhole's bit for bit as the lens shrinks.
+BDPT_HD f3 lens_ray_dir(const DCam& c, float F, f3 pl, float x, float y) {
+  const f3 pf = mk3((2 * x - 1) * c.tanh_, (2 * y - 1) * c.tanv_, -1.0f);
+  return normalize(cam_to_world(c, sub(pf, divs(pl, F))));
+}
+// camera_sample from the lens point pl: its expressions with cam -> x_l, the raster position
+// taken through the focal plane (q = pLens + (wc / wc.z) F, used as q / F = pLens / F + wc / wc.z).
+BDPT_HD EyeSample camera_sample_lens(const DCam& c, float F, int W, int H, f3 pl, f3 p) {
+  EyeSample e;
+  const f3 xl = lens_world(c, pl);
+  f3 wi = sub(xl, p);
+  float dist = norm(wi);
+  wi = normalize(wi);
+  f3 mw = neg(wi);
+  f3 wc = add(add(smul(mw.x, mk3(c.w2c[0], c.w2c[1], c.w2c[2])), smul(mw.y, mk3(c.w2c[3], c.w2c[4], c.w2c[5]))),
+              smul(mw.z, mk3(c.w2c[6], c.w2c[7], c.w2c[8])));
+  wc.z = -wc.z;
+  float ct = wc.z;
+  float c2 = ct * ct;
+  float denom = 4 * c.tanh_ * c.tanv_ / (c2 * c2);
+  e.dir_pdf = (dist * dist) / ct;
+  e.n = neg(wi);
+  float rz = 1.0f / wc.z;
+  wc = mk3(wc.x * rz, wc.y * rz, wc.z * rz);
+  const float qx = pl.x / F + wc.x, qy = pl.y / F + wc.y;
+  float fx = ((qx / c.tanh_ + 1) * 0.5f) * (float)W;
+  float fy = ((qy / c.tanv_ + 1) * 0.5f) * (float)H;
+  e.x = (fx > -1.0f && fx < (float)W) ? (int)fx : -1;
+  e.y = (fy > -1.0f && fy < (float)H) ? (int)fy : -1;
+  e.alpha = divs(splat3(1.0f / denom), 1.0f);
+  e.pos = xl;
   e.zh = zaxis(e.n);
   return e;
 }
@@ -485,6 +553,13 @@ BDPT_HD void walk_begin(const SceneView& S, const SampleParams& sp, Paths<MAXV>&
   w.l1env = false;   // re-read with the rest when the light walk starts
   // the walk: eye first (camera ray on [nClip, fClip], alpha = 1, pdf = 1, n = d), then light
   w.ro = cam;
+  if (EXT >= 3) {
+    // §9b: E[1] is the lens point (its two uniforms on a sub-stream of their own: every other draw
+    // of the sample is the pinhole kernels'), the ray runs to the focal plane's point of (dx, dy)
+    const f3 pl = lens_draw(S.cam, g, RNG_LENS_WALK);
+    w.ro = lens_world(S.cam, pl);
+    rd = lens_ray_dir(S.cam, sp.focal, pl, dx, dy);
+  }
   w.rmin = S.cam.nclip;
   w.rmax = S.cam.fclip;
   w.prev_n = rd;
@@ -762,6 +837,7 @@ BDPT_HD int make_conn(const SceneView& S, const SampleParams& sp, const PA& P, R
           light_contains(S.lights[l], ev.pos)) { eye_light = l; break; }
     if (eye_light < 0) return CONN_NONE;
     f3 prevp = i == 2 ? cam : P.e(i - 1).pos;
+    if (EXT >= 3 && i == 2) prevp = lens_world(S.cam, lens_draw(S.cam, g, RNG_LENS_WALK));   // this sample's walk lens point
     f3 wi = normalize(sub(ev.pos, prevp));
     const DLight& EL = S.lights[eye_light];
     if (!(light_dir_pdf(EL, wi) > 0)) return CONN_NONE;
@@ -777,8 +853,11 @@ BDPT_HD int make_conn(const SceneView& S, const SampleParams& sp, const PA& P, R
   lv = lv_pre ? *lv_pre : P.l(j);   // j == 1: the original L[1] (MIS quirk); j >= 2: the light endpoint
   if (j >= 2 && !can_connect(lv)) return CONN_NONE;
   f3 vl_pos, vl_n, la;
+  // §9b: a camera connection's own lens point (camera space), fresh per j and independent of the walk's
+  f3 pl = splat3(0);
+  if (EXT >= 3 && eye_cam) pl = lens_draw(S.cam, g, RNG_LENS_CONN + (uint32_t)j);
   if (j == 1) {   // fresh light sample (bidirection.cpp:332-358)
-    const f3 epos = eye_cam ? cam : ev.pos;
+    const f3 epos = eye_cam ? (EXT >= 3 ? lens_world(S.cam, pl) : cam) : ev.pos;
     rng_stream(g, 2u + (uint32_t)i);
     int id = (int)(rng_next(g) * (float)S.nlights);
     if (id >= S.nlights) id = S.nlights - 1;
@@ -799,7 +878,7 @@ BDPT_HD int make_conn(const SceneView& S, const SampleParams& sp, const PA& P, R
   }
   f3 ve_pos, ve_n, ea;
   if (eye_cam) {   // camera sample (bidirection.cpp:360-383)
-    es = camera_sample(S.cam, sp.W, sp.H, vl_pos);
+    es = EXT >= 3 ? camera_sample_lens(S.cam, sp.focal, sp.W, sp.H, pl, vl_pos) : camera_sample(S.cam, sp.W, sp.H, vl_pos);
     if (!(es.x >= 0 && es.y >= 0 && es.x < sp.W && es.y < sp.H)) return CONN_NONE;   // not splatted
     ve_pos = es.pos; ve_n = es.n; ea = es.alpha;
   } else {

@@ -604,6 +604,7 @@ int build_host_scene(const bdpt_scene_desc* d, HostScene& out, std::string& err,
   out.cam.tanv_ = (float)std::tan(c.vfov_deg * PI_D / 360);
   out.cam.nclip = (float)c.nclip;
   out.cam.fclip = (float)c.fclip;
+  out.cam.lens_r = 0.0f;   // the pinhole; bdpt_create sets the thin lens
 
   // primitive bboxes (triangle.cpp:9-21 / sphere.h:32-34)
   const int n = d->nprim;

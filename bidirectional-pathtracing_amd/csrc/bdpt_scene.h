@@ -61,10 +61,14 @@ struct HostScene {
 };
 
 // Which k_bdpt_sample flavour renders a scene (the EXT template parameter, bdpt_paths.h): 2 with an
-// accepted hemisphere / directional light, 1 with an environment map or roulette, else 0.
-inline int kernel_flavour(const HostScene& hs, bool roulette) {
-  return hs.inf_lights > 0 ? 2 : (hs.env_light >= 0 || roulette) ? 1 : 0;
+// accepted hemisphere / directional light, 1 with an environment map or roulette, else 0; 3 with a
+// thin lens (bdpt_params.lens_radius > 0, §9b), whatever the scene holds.
+inline int kernel_flavour(const HostScene& hs, bool roulette, bool lens = false) {
+  return lens ? 3 : hs.inf_lights > 0 ? 2 : (hs.env_light >= 0 || roulette) ? 1 : 0;
 }
+
+// bdpt_params.focal_distance as the kernels take it: 0 (or less) means 4.7, the PathTracer's rule.
+inline float lens_focal(double focal_distance) { return (float)(focal_distance > 0 ? focal_distance : 4.7); }
 
 constexpr int kTopNodes = 1024;
 // Spatial splits in the device tree (SBVH, bdpt_scene.cpp SahBuilder): tried at a node whose best

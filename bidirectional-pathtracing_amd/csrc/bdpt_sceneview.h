@@ -58,7 +58,10 @@ struct DCam {
   float w2c[9];
   float tanh_, tanv_;  // tan(hFov*PI/360) in fp64, rounded (camera.cpp:199-200)
   float nclip, fclip;
+  float lens_r;        // thin-lens radius, read by the lens kernels (EXT = 3) only; it
+                       // fills what was the struct's tail padding inside SceneView, so nothing moves
 };
+static_assert(sizeof(DCam) == 26 * sizeof(float), "DCam: 25 floats + the lens radius");
 
 // Child reference: >= 0 internal node index; < 0 leaf: ~ref = start << 7 | sphere_mask << 3 | count.
 BDPT_HD bool ref_is_leaf(int r) { return r < 0; }

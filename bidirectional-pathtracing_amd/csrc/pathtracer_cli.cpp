@@ -3,7 +3,7 @@
 //
 //   pathtracer [-s spp] [-m max_depth] [-r W H] [-f out.png] [-p x y dx dy] [-t threads] [-c cam.txt]
 //              [-l n] [-e envmap.exr] [--rr] [--infinite-lights] [-g gpus] [-S seed] [--dump-scene scene.json]
-//              [--pt [-a batch tol] [-H] [-b lens] [-d focal]] scene.dae
+//              [--pt [-a batch tol] [-H] [-b lens] [-d focal]] [--thin-lens [-b lens] [-d focal]] scene.dae
 //
 // Same flags and defaults as the reference (-s 1, -m 1, 800x600 when -r is absent; -t / -l are
 // accepted and do not apply to the GPU path; -p renders one cell). -g N splits the sample range
@@ -13,6 +13,8 @@
 // reference cannot run with it; --rr turns on Russian roulette (bidirection.cpp:87-93);
 // --infinite-lights lets BDPT render ambient and directional lights (bdpt_params.infinite_lights,
 // DESIGN.md §9a), which it otherwise rejects as the reference's BDPT cannot run them.
+// --thin-lens gives BDPT the PathTracer's thin-lens camera (-b, -d and a -c file's last line, in the
+// PathTracer's order); without it BDPT is the pinhole whatever -b, -d and -c say.
 // --pt selects the reference's unidirectional PathTracer (pathtracer.cpp:47-340) with its flags
 // -l, -a, -H, -b, -d (main.cpp:107-141); its -g N splits the frame into row bands (whole pixels).
 // Output: the tonemapped PNG and the "_rate.png" sampling-rate image, as render_to_file writes
@@ -45,8 +47,9 @@ void usage(const char* b) {
   printf("  --pt             Unidirectional PathTracer instead of BDPT\n");
   printf("  -a  <INT> <FLOAT> PathTracer: samples per batch and tolerance (adaptive sampling)\n");
   printf("  -H               PathTracer: hemisphere sampling for direct lighting\n");
-  printf("  -b  <FLOAT>      PathTracer: lens radius\n");
-  printf("  -d  <FLOAT>      PathTracer: focal distance\n");
+  printf("  -b  <FLOAT>      PathTracer, or BDPT with --thin-lens: lens radius\n");
+  printf("  -d  <FLOAT>      PathTracer, or BDPT with --thin-lens: focal distance\n");
+  printf("  --thin-lens      BDPT: thin-lens camera from -b, -d and the -c file (ignored without it)\n");
   printf("  -e  <PATH>       Path to environment map\n");
   printf("  --rr             Russian roulette on both subpaths\n");
   printf("  --infinite-lights  BDPT: render ambient and directional lights (rejected without it;\n"
@@ -78,7 +81,7 @@ int main(int argc, char** argv) {
   unsigned long long seed = 5489;
   std::string out, dump, scene, envpath, cam_settings;
   std::vector<int> devices;
-  bool rr = false, pt = false, hemi = false, stats = true, inf_lights = false;
+  bool rr = false, pt = false, hemi = false, stats = true, inf_lights = false, thin_lens = false;
   int nal = 1, batch = 32;
   float tol = 0.05f;
   double lens = 0.0, focal = 4.7;
@@ -115,6 +118,7 @@ int main(int argc, char** argv) {
     else if (a == "-e") { need(1); envpath = argv[++i]; }
     else if (a == "--rr") rr = true;
     else if (a == "--infinite-lights") inf_lights = true;
+    else if (a == "--thin-lens") thin_lens = true;
     else if (a == "--no-stats") stats = false;
     else if (a == "--tonemap") {
       need(4);
@@ -162,6 +166,11 @@ int main(int argc, char** argv) {
   }
   fprintf(stderr, "[PathTracer] %d primitives, %d materials, %d lights; %dx%d, %d spp, max depth %d, %d GPU(s)\n",
           desc.nprim, desc.nmat, desc.nlight, w, h, spp, max_depth, gpus);
+  // BDPT's camera: the thin lens only with --thin-lens (-c files carry a lens radius, and BDPT has
+  // always rendered them as the pinhole)
+  const bool bdpt_lens = !pt && thin_lens && lens > 0;
+  if (bdpt_lens) fprintf(stderr, "[PathTracer] BDPT camera: thin lens, radius %g, focal distance %g\n", lens, focal > 0 ? focal : 4.7);
+  else if (!pt) fprintf(stderr, "[PathTracer] BDPT camera: pinhole\n");
 
   std::vector<bdpt_tile> tiles;
   if (cx >= 0) tiles.push_back(bdpt_tile{(int32_t)cx, (int32_t)cy, (int32_t)cdx, (int32_t)cdy});
@@ -183,6 +192,8 @@ int main(int argc, char** argv) {
       p.integrator = BDPT_INTEGRATOR_PT;
       p.ns_area_light = nal; p.samples_per_batch = batch; p.max_tolerance = tol;
       p.direct_hemisphere_sample = hemi ? 1 : 0; p.lens_radius = lens; p.focal_distance = focal;
+    } else if (bdpt_lens) {
+      p.lens_radius = lens; p.focal_distance = focal;
     }
     return p;
   };

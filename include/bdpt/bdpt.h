@@ -165,6 +165,10 @@ typedef struct bdpt_params {
   int32_t samples_per_batch;  /* -a batch: adaptive sampling batch (0 = 32)                  */
   float max_tolerance;        /* -a tol: stop when 1.96 sigma / sqrt(n) <= tol * mean        */
   int32_t direct_hemisphere_sample;  /* -H: hemisphere instead of light sampling            */
+  /* The thin lens (Camera::generate_ray_for_thin_lens). The PathTracer always honoured the two; under
+   * BDPT_INTEGRATOR_BDPT lens_radius > 0 now selects the thin-lens kernels (a lens
+   * point per eye walk and a fresh one per camera connection) and lens_radius <= 0 is the pinhole,
+   * which a caller that zeroes the struct gets as before. Same layout, same ABI version. */
   double lens_radius;         /* -b (0: pinhole)                                             */
   double focal_distance;      /* -d (0 = 4.7)                                                */
   /* Was reserved[0]: the layout is unchanged and a caller that zeroes the reserved words gets the

@@ -29,8 +29,9 @@ cmd = [ge.HIPCC] + [f for f in ge.HIP_FLAGS if f not in ("-fPIC",)] + [
     os.path.join(CS, "bdpt_hip.hip"), "-o", out] + extra
 subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
 s = open(out).read().split("\n")
-want = re.compile(r"^_ZN12_GLOBAL__N_1(?:13k_bdpt_sampleILi(\d+)ELb0ELi(\d)ELi(\d)EEEvNS_7KParamsE|"
-                  r"4k_ptILb0ELi(\d)EEEvNS_9PtKParamsE):")
+# k_bdpt_sample lives in namespace bdpt (bdpt_megakernel.h), k_pt in bdpt_hip.hip's anonymous one
+want = re.compile(r"^_ZN(?:4bdpt13k_bdpt_sampleILi(\d+)ELb0ELi(\d)ELi(\d)EEEvNS_7KParamsE|"
+                  r"12_GLOBAL__N_14k_ptILb0ELi(\d)EEEvNS_9PtKParamsE):")
 for i, line in enumerate(s):
     m = want.match(line)
     if not m:
