@@ -177,6 +177,12 @@ inline unsigned long long* step_hist() { static thread_local unsigned long long 
 inline int& step_hist_nested() { static thread_local int n = 0; return n; }
 // diagnostics: the any-hit queries' rays (o, d, tmin, tmax) while a sink is set (tools/anyhit_probe.py)
 inline std::vector<float>*& ray_dump() { static thread_local std::vector<float>* v = nullptr; return v; }
+// diagnostics: while a sink is set, a log of int triples (tools/flush_sim.py). Every any-hit query
+// adds (tag, node steps, primitive tests), tag = anyhit_tag() as render_sample set it (i << 8 | j);
+// render_sample opens each pixel-sample with (-1, conn_e mask, conn_l mask) and (-2, src_e mask, nL),
+// the lists the megakernel's connect_sample walks (masks cut to 32 bits: depths up to 30).
+inline std::vector<int>*& anyhit_log() { static thread_local std::vector<int>* v = nullptr; return v; }
+inline int& anyhit_tag() { static thread_local int t = 0; return t; }
 #endif
 template <int K>
 struct TravStack {
@@ -724,13 +730,17 @@ BDPT_HD bool trace_any(const SceneView& S, f3 o, f3 d, float tmin, float tmax, C
 #if defined(BDPT_STEP_HIST) && !defined(__HIP_DEVICE_COMPILE__)
   struct StepHistAny {   // any-hit queries: histogram entries 256..511
     const Counters& c;
-    uint32_t n0;
+    uint32_t n0, p0;
     ~StepHistAny() {
       if (step_hist_nested()) return;
       const uint32_t s = (c.nodes - n0) / (uint32_t)lm_width(LM);
       step_hist()[256 + (s < 255 ? s : 255)]++;
+      if (anyhit_log()) {
+        const int e[3] = {anyhit_tag(), (int)s, (int)(c.tris + c.sphs - p0)};
+        anyhit_log()->insert(anyhit_log()->end(), e, e + 3);
+      }
     }
-  } step_hist_{c, c.nodes};
+  } step_hist_{c, c.nodes, c.tris + c.sphs};
   if (ray_dump() && !step_hist_nested()) {
     const float rv[8] = {o.x, o.y, o.z, d.x, d.y, d.z, tmin, tmax};
     ray_dump()->insert(ray_dump()->end(), rv, rv + 8);
@@ -741,6 +751,121 @@ BDPT_HD bool trace_any(const SceneView& S, f3 o, f3 d, float tmin, float tmax, C
   int stack_mem[kStackMax];
   TravStack<K> stk(stack_mem, LM == 1 || LM == 2 ? lane_stack(S) : nullptr);
   return traverse<LM, K>(S, r, stk, tmin, q, c);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The resumable any-hit traversal (the megakernel's connection-ray flush, bdpt_megakernel.h): the
+// query's state lives in a struct of the caller's, and the traversal hands the wave back at a phase
+// boundary of the while-while loop (after a leaf batch) once enough lanes have ended their query for
+// the caller to give them the next queued ray. A connection ray carries nothing but its ring slot,
+// so a lane that ends early costs the wave one live register instead of idling until the slowest of
+// the 64 rays ends (E[max of 64] is 27 node steps against a mean of 4.5 on the north star's tree).
+// LM 3's flat list has no divergence to fill (round 2: -6 % on CBspheres), so it keeps trace_any.
+BDPT_HD constexpr bool flush_refill(int LM) { return LM == 0 || LM == 2; }
+// lanes of the wave that must have ended before the traversal returns for a refill
+constexpr int kRefillIdle = 16;
+
+template <int K>
+struct AnyTrav {
+  RayInv r;
+  float tmax;
+  int ref;    // the node / leaf to continue with; kTravDone: no query in flight (ended, or none taken yet)
+  bool hit;   // of the query that ended last
+  BDPT_HD bool ended() const { return ref == kTravDone; }
+  BDPT_HD void start(const SceneView& S, TravStack<K>& stk, f3 o, f3 d, float tmax_) {
+    r = make_rayinv(o, d);
+    tmax = tmax_;
+    ref = S.root;
+    hit = false;
+    stk.clear();
+  }
+};
+
+// any-hit test of leaf lf's primitives (traverse()'s test_leaf under AnyQuery)
+template <int LM>
+BDPT_HD bool any_leaf(const SceneView& S, f3 o, f3 d, float tmin, float tmax, int lf, Counters& c) {
+  const int st = leaf_start(lf), cnt = leaf_count(lf), sm = leaf_sph_mask(lf);
+  float4 a0, a1, a2;
+  if constexpr (leaf_prefetch(LM)) {
+    ld_rec3<LM>(S, st, a0, a1, a2);
+  }
+  for (int k = 0; k < cnt; k++) {
+    BDPT_LANE_PROF(c, LP_APRIM);
+    const int pi = st + k;
+    float4 g0, g1, g2;
+    if constexpr (leaf_prefetch(LM)) {
+      // this record was loaded one test ahead; issue the next one's loads (if any) before testing it
+      g0 = a0; g1 = a1; g2 = a2;
+      if (k + 1 < cnt) ld_rec3<LM>(S, pi + 1, a0, a1, a2);
+    }
+    float t, b1, b2;
+    if ((sm >> k) & 1) {
+      c.sphs++;
+      if (!leaf_prefetch(LM)) g0 = ld_geom<LM>(S, 3 * pi);
+      if (sph_test(g0, o, d, tmin, tmax, &t)) return true;
+    } else {
+      c.tris++;
+      if (!leaf_prefetch(LM)) { g0 = ld_geom<LM>(S, 3 * pi); g1 = ld_geom<LM>(S, 3 * pi + 1); g2 = ld_geom<LM>(S, 3 * pi + 2); }
+      if (tri_test(g0, g1, g2, o, d, tmin, tmax, &t, &b1, &b2)) return true;
+    }
+  }
+  return false;
+}
+
+// Runs the wave's queries in flight (lanes with !q.ended()) on [tmin, q.tmax] in trace_any's visiting
+// order, and returns at a phase boundary when every lane has ended, or, if the caller has more rays
+// to hand out, when at least kRefillIdle lanes have. A lane that ended holds its answer in q.hit.
+// The exit test is wave-uniform: every lane of the wave calls this together, ended ones included.
+template <int LM, int K>
+BDPT_HD void traverse_any_resumable(const SceneView& S, AnyTrav<K>& q, TravStack<K>& stk, float tmin, bool more,
+                                    Counters& c) {
+  static_assert(LM != 3, "the flat list has no resumable form");
+  int ref = q.ref;
+  bool hit = q.hit;
+  for (;;) {
+    if constexpr (spec_trav(LM)) {
+      // speculative while-while, as in traverse(); no leaf is postponed across a phase boundary
+      int pend = 0;
+      while (ref >= 0) {
+        BDPT_LANE_PROF(c, LP_ANODE);
+        ref = node_step<K, LM, kAnyOrd>(S, q.r, ref, tmin, q.tmax, stk, c);
+        if ((ref < 0) & (ref != kTravDone) & (pend == 0)) {
+          pend = ref;
+          if (!stk.pop(ref)) ref = kTravDone;
+        }
+        if (wave_count((pend == 0) & (ref >= 0)) == 0) break;
+      }
+      while (pend != 0) {
+        if (any_leaf<LM>(S, q.r.o, q.r.d, tmin, q.tmax, pend, c)) {
+          hit = true;
+          ref = kTravDone;
+          break;
+        }
+        pend = 0;
+        if ((ref < 0) & (ref != kTravDone)) {
+          pend = ref;
+          if (!stk.pop(ref)) ref = kTravDone;
+        }
+      }
+    } else {
+      while (ref >= 0) {
+        BDPT_LANE_PROF(c, LP_ANODE);
+        ref = node_step<K, LM, kAnyOrd>(S, q.r, ref, tmin, q.tmax, stk, c);
+      }
+      if (ref != kTravDone) {
+        if (any_leaf<LM>(S, q.r.o, q.r.d, tmin, q.tmax, ref, c)) {
+          hit = true;
+          ref = kTravDone;
+        } else if (!stk.pop(ref)) {
+          ref = kTravDone;
+        }
+      }
+    }
+    const int n_ended = wave_count(ref == kTravDone);
+    if (n_ended == wave_count(true) || (more && n_ended >= kRefillIdle)) break;
+  }
+  q.ref = ref;
+  q.hit = hit;
 }
 
 // Shading record of a closest hit: interpolated normal (triangle.cpp:80-82) or sphere normal

@@ -76,29 +76,13 @@ __device__ __forceinline__ float wave_sumf(float v) {
   return v;
 }
 
-// Resolve n (<= 64) queued connection rays, one per lane: any-hit test, then add the value of the
-// unoccluded ones to the owner's eye accumulator (LDS atomic) or splat it (global atomic).
-// Splats aimed at the flush's most common kind of target — the first splatting lane's pixel — are
+// The unoccluded connection rays of the lanes with vis set: each adds its value to the owner's eye
+// accumulator (LDS atomic) or splats it (global atomic).
+// Splats aimed at the round's most common kind of target — the first splatting lane's pixel — are
 // summed across the wave first: a point light's own vertex projects to the same pixel for every
 // sample (t = 1, s = 1), and unaggregated that one address serialises ~all global atomics.
-template <int LM>
-__device__ __forceinline__ void flush_queue(const SceneView& S, WaveQ& q, int head, int n, int lane, float* light,
-                                            Counters& cnt) {
-  bool vis = false;
-  float vx = 0, vy = 0, vz = 0;
-  int tgt = -1;
-#ifdef BDPT_PHASE_PROF
-  if (lane == 0) cnt.lp[2 * LP_FLUSH]++;
-  if (lane < n) cnt.lp[2 * LP_FLUSH + 1]++;
-#endif
-  if (lane < n) {
-    const int k = (head + lane) & (QCAP - 1);
-    f3 o = mk3(q.ox[k], q.oy[k], q.oz[k]), d = mk3(q.dx[k], q.dy[k], q.dz[k]);
-    const float tmax = q.tmax[k];
-    vx = q.vx[k]; vy = q.vy[k]; vz = q.vz[k];
-    tgt = q.tgt[k];
-    vis = !trace_any<LM, kConnStack>(S, o, d, BDPT_EPS_F, tmax, cnt);
-  }
+__device__ __forceinline__ void resolve_rays(WaveQ& q, bool vis, float vx, float vy, float vz, int tgt, int lane,
+                                             float* light) {
   if (vis && tgt < 0) {
     const int ow = ~tgt;
     atomicAdd(&q.acc[0][ow], vx);
@@ -134,11 +118,81 @@ __device__ __forceinline__ void flush_queue(const SceneView& S, WaveQ& q, int he
   }
 }
 
+// Resolve the n queued connection rays from ring position head on.
+// LM 3 (n <= 64): one ray per lane, an any-hit test each, then resolve_rays.
+// With refill (flush_refill(LM), any n <= QCAP): lanes 0-63 take the first rays; whenever the
+// resumable traversal hands the wave back, the lanes whose ray ended resolve it (value and target
+// re-read from the ring slot) and take the next slots in lane order from a wave-uniform cursor,
+// until every ray queued at the start is traced. Across the traversal a lane holds, beyond the
+// traversal's own state, its slot index alone. Nothing is pushed during a flush, so a slot stays
+// valid until its lane has resolved it.
+template <int LM>
+__device__ __forceinline__ void flush_queue(const SceneView& S, WaveQ& q, int head, int n, int lane, float* light,
+                                            Counters& cnt) {
+#ifdef BDPT_PHASE_PROF
+  if (lane == 0) cnt.lp[2 * LP_FLUSH]++;
+#endif
+  if constexpr (flush_refill(LM)) {
+    AnyTrav<kConnStack> st = {};
+    st.ref = kTravDone;
+    int stack_mem[kStackMax];
+    TravStack<kConnStack> stk(stack_mem, LM == 1 || LM == 2 ? lane_stack(S) : nullptr);
+    int slot = -1;   // this lane's ring slot, -1: none
+    int cur = head;  // wave-uniform: the next ring position to hand out
+    const int end = head + n;
+    for (;;) {
+      const bool want = slot < 0;
+      const unsigned long long mw = __ballot(want);
+      const int pos = cur + lanes_below(mw);
+      if (want && pos < end) {
+        slot = pos & (QCAP - 1);
+        st.start(S, stk, mk3(q.ox[slot], q.oy[slot], q.oz[slot]), mk3(q.dx[slot], q.dy[slot], q.dz[slot]),
+                 q.tmax[slot]);
+        cnt.shadow++;
+#ifdef BDPT_PHASE_PROF
+        cnt.lp[2 * LP_FLUSH + 1]++;
+#endif
+      }
+      cur = __builtin_amdgcn_readfirstlane(min(end, cur + (int)__popcll(mw)));
+      if (__ballot(slot >= 0) == 0) break;
+      traverse_any_resumable<LM, kConnStack>(S, st, stk, BDPT_EPS_F, cur < end, cnt);
+      const bool ended = (slot >= 0) & st.ended();
+      const bool vis = ended & !st.hit;
+      float vx = 0, vy = 0, vz = 0;
+      int tgt = -1;
+      if (vis) {
+        vx = q.vx[slot]; vy = q.vy[slot]; vz = q.vz[slot];
+        tgt = q.tgt[slot];
+      }
+      resolve_rays(q, vis, vx, vy, vz, tgt, lane, light);
+      if (ended) slot = -1;
+    }
+  } else {
+    bool vis = false;
+    float vx = 0, vy = 0, vz = 0;
+    int tgt = -1;
+#ifdef BDPT_PHASE_PROF
+    if (lane < n) cnt.lp[2 * LP_FLUSH + 1]++;
+#endif
+    if (lane < n) {
+      const int k = (head + lane) & (QCAP - 1);
+      f3 o = mk3(q.ox[k], q.oy[k], q.oz[k]), d = mk3(q.dx[k], q.dy[k], q.dz[k]);
+      const float tmax = q.tmax[k];
+      vx = q.vx[k]; vy = q.vy[k]; vz = q.vz[k];
+      tgt = q.tgt[k];
+      vis = !trace_any<LM, kConnStack>(S, o, d, BDPT_EPS_F, tmax, cnt);
+    }
+    resolve_rays(q, vis, vx, vy, vz, tgt, lane, light);
+  }
+}
+
 // k_bdpt_sample: each lane owns one pixel and a chunk of its samples. Per sample the lane builds
 // both subpaths (random walks, closest-hit traversal) and then enumerates its (i, j) connections
 // in the reference's order; every connection that needs a visibility ray is pushed (ballot +
 // mbcnt compaction) into the wave's LDS ring, and whenever 64 are queued the whole wave traces
-// them together — all 64 lanes busy on shadow rays regardless of per-lane path lengths.
+// them together — all 64 lanes busy on shadow rays regardless of per-lane path lengths. Where the
+// any-hit traversal diverges (LM 0 / 2, flush_refill) the wave instead lets the ring fill up and
+// drains it whole, lanes whose ray ends early taking the next queued one (flush_queue).
 // 4 waves per SIMD = 128 VGPRs: measured best (round 1: 2: 160, 3: 220, 4: 259, 5: 151 Msamples/s;
 // round 4, with 0 instead of 38-51 spilled VGPRs at 3 waves: still -13..-16% on every workload,
 // profiles/r04c_ab_waves.log)
@@ -297,7 +351,7 @@ struct ConnState {
 // vertices, so the j == 1 (fresh light sample) and i == 1 (camera connection) bodies run once per
 // iteration for all lanes instead of interleaving with the general case; every connection that
 // needs a visibility ray is pushed (ballot + mbcnt compaction) into the wave's LDS ring, and
-// whenever 64 are queued the wave traces them together. PA: the path accessor (PathsInRegs over the
+// whenever a flush is due (conn_step) the wave traces them together. PA: the path accessor (PathsInRegs over the
 // lane's private Paths).
 template <int LM, int EXT, bool STATS, class PA>
 __device__ __forceinline__ void connect_sample(const KParams& kp, WaveQ& q, const PA& PP, Rng& g, int nE, int nL,
@@ -307,8 +361,10 @@ __device__ __forceinline__ void connect_sample(const KParams& kp, WaveQ& q, cons
   unsigned long long tp0, tp1;
 #endif
   // one (i, j) connection per lane (active lanes only), its ray pushed into the wave's ring, the
-  // ring flushed whenever 64 rays are queued
-  auto conn_step = [&](int i, int j, bool active, const Vtx* ev_pre = nullptr, const Vtx* lv_pre = nullptr) {
+  // ring flushed when it is due: 64 rays queued (LM 3), or no room left for the next step's pushes,
+  // of which there are at most next_max (wave-uniform)
+  auto conn_step = [&](int i, int j, bool active, int next_max, const Vtx* ev_pre = nullptr,
+                       const Vtx* lv_pre = nullptr) {
     int kind = CONN_NONE;
     Conn cn;
     if (active) {
@@ -336,13 +392,18 @@ __device__ __forceinline__ void connect_sample(const KParams& kp, WaveQ& q, cons
       q.tgt[slot] = eye_t ? ~lane : cn.splat;
     }
     cs.tail += __popcll(m);
-    if (cs.tail - cs.head >= 64) {
+    // With refill a flush drains the ring, and the later it runs the more rays it has to fill idle
+    // lanes with: only when the next step's pushes (at most next_max) could overflow the ring. The
+    // test stays behind the push, so that cn is never live across a flush.
+    const int queued = cs.tail - cs.head;
+    if (flush_refill(LM) ? queued + next_max > QCAP : queued >= 64) {
+      const int n = flush_refill(LM) ? queued : 64;
       PH_STAMP(tp0);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      flush_queue<LM>(kp.S, q, cs.head, 64, lane, kp.light, cnt);
+      flush_queue<LM>(kp.S, q, cs.head, n, lane, kp.light, cnt);
       __builtin_amdgcn_wave_barrier();
-      cs.head += 64;
+      cs.head += n;
       PH_STAMP(tp1);
 #ifdef BDPT_PHASE_PROF
       cs.ph_flush += tp1 - tp0;
@@ -361,12 +422,16 @@ __device__ __forceinline__ void connect_sample(const KParams& kp, WaveQ& q, cons
   // lanes), every lane walking its own list in the reference's index order, so the wave iterates
   // the longest list instead of the longest subpath: s = 0 (j = 0), the fresh light sample (j = 1:
   // the camera, i = 1, and every connectable eye vertex), light tracing to the camera (i = 1, j >= 2)
+  // The next step pushes at most one ray per lane whose list is not yet empty: the loops' own ballot
+  // counts them. After a list's last step any strategy may follow, a new sample's included: 64.
   auto each = [&](Mask m, int fixed, bool fixed_is_j) {
-    while (__ballot(m != 0)) {
+    unsigned long long left = __ballot(m != 0);
+    while (left) {
       const bool act = m != 0;
       const int k = act ? ctz_mask(m) : 0;
-      conn_step(fixed_is_j ? k : fixed, fixed_is_j ? fixed : k, act);
       if (act) m &= m - 1;
+      left = __ballot(m != 0);
+      conn_step(fixed_is_j ? k : fixed, fixed_is_j ? fixed : k, act, left ? (int)__popcll(left) : 64);
     }
   };
   each(m0, 0, true);
@@ -377,14 +442,16 @@ __device__ __forceinline__ void connect_sample(const KParams& kp, WaveQ& q, cons
   // grid are empty for most lanes)
   if (mL == 0) mE = 0;
   Mask jm = mL;
-  while (__ballot(mE != 0)) {
+  unsigned long long left = __ballot(mE != 0);
+  while (left) {
     const bool act = mE != 0;
     const int ci = act ? ctz_mask(mE) : 0, cj = act ? ctz_mask(jm) : 0;
-    conn_step(ci, cj, act);
     if (act) {
       jm &= jm - 1;
       if (jm == 0) { mE &= mE - 1; jm = mL; }
     }
+    left = __ballot(mE != 0);
+    conn_step(ci, cj, act, left ? (int)__popcll(left) : 64);
   }
 #ifdef BDPT_PHASE_PROF
   cs.ph_gen += __builtin_amdgcn_s_memtime() - tg0;

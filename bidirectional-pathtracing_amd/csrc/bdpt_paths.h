@@ -935,6 +935,12 @@ BDPT_HD f3 render_sample(const SceneView& S, const SampleParams& sp, Paths<MAXV>
   Rng g;
   prepare_sample<MAXV, LM, EXT>(S, sp, P, cnt, g, x, y, sample);
   f3 eye_sum = splat3(0);
+#if defined(BDPT_STEP_HIST) && !defined(__HIP_DEVICE_COMPILE__)
+  if (anyhit_log()) {   // diagnostics: this pixel-sample's connection lists (tools/flush_sim.py)
+    const int e[6] = {-1, (int)(uint32_t)P.cE, (int)(uint32_t)P.cL, -2, (int)(uint32_t)P.sE, P.nL};
+    anyhit_log()->insert(anyhit_log()->end(), e, e + 6);
+  }
+#endif
   for (int i = 1; i < P.nE; i++) {
     for (int j = 0; j < P.nL; j++) {
       Conn cn;
@@ -942,6 +948,9 @@ BDPT_HD f3 render_sample(const SceneView& S, const SampleParams& sp, Paths<MAXV>
       if (kind == CONN_DIRECT) {
         eye_sum = add(eye_sum, cn.val);
       } else if (kind == CONN_RAY) {
+#if defined(BDPT_STEP_HIST) && !defined(__HIP_DEVICE_COMPILE__)
+        anyhit_tag() = i << 8 | j;
+#endif
         if (trace_any<LM>(S, cn.o, cn.d, BDPT_EPS_F, cn.tmax, cnt)) continue;
         if (cn.splat >= 0) sink.splat(cn.splat % sp.W, cn.splat / sp.W, cn.val);
         else eye_sum = add(eye_sum, cn.val);
