@@ -79,6 +79,13 @@ class Params(C.Structure):
 INTEGRATOR_BDPT, INTEGRATOR_PT = 0, 1
 
 
+class DenoiseParams(C.Structure):
+    """bdpt_denoise_params: the a-trous filter's settings. denoise_params() fills
+    the library's defaults."""
+    _fields_ = [("levels", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("demodulate", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class Tile(C.Structure):
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
 
@@ -343,6 +350,15 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.bdpt_reduce_ranks.argtypes = [C.c_void_p]
     lib.bdpt_reduce_destroy.argtypes = [C.c_void_p]
     lib.bdpt_reduce_destroy.restype = None
+    lib.bdpt_render_features.argtypes = [C.c_void_p, C.POINTER(Tile), C.c_int32, C.c_int32]
+    lib.bdpt_read_features.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    lib.bdpt_features_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.bdpt_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
+    lib.bdpt_denoise.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DenoiseParams)]
+    lib.bdpt_read_denoised.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    lib.bdpt_denoised_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.bdpt_denoise_buffers.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                         C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -356,6 +372,61 @@ def _check(rc: int, lib) -> None:
     if rc != BDPT_OK:
         msg = lib.bdpt_last_error()
         raise BDPTError(f"bdpt error {rc}: {msg.decode() if msg else ''}")
+
+
+def denoise_params(levels: Optional[int] = None, sigma_color: Optional[float] = None,
+                   sigma_normal: Optional[float] = None, sigma_depth: Optional[float] = None,
+                   demodulate: Optional[bool] = None) -> DenoiseParams:
+    """The library's default filter settings (bdpt_denoise_default_params) with the given ones
+    replaced."""
+    lib = load_library()
+    p = DenoiseParams()
+    _check(lib.bdpt_denoise_default_params(C.byref(p)), lib)
+    if levels is not None:
+        p.levels = levels
+    if sigma_color is not None:
+        p.sigma_color = sigma_color
+    if sigma_normal is not None:
+        p.sigma_normal = sigma_normal
+    if sigma_depth is not None:
+        p.sigma_depth = sigma_depth
+    if demodulate is not None:
+        p.demodulate = 1 if demodulate else 0
+    return p
+
+
+def denoise_buffers(color_ptr: int, features_ptr: int, width: int, height: int, out_ptr: int,
+                    device: int = 0, stream: int = 0, **params) -> None:
+    """bdpt_denoise_buffers: the a-trous filter over raw device pointers (color W*H*3 floats,
+    features W*H*8 floats, out W*H*3 floats, which may be the colour buffer) on `stream`."""
+    lib = load_library()
+    p = denoise_params(**params)
+    _check(lib.bdpt_denoise_buffers(device, C.c_void_p(color_ptr), C.c_void_p(features_ptr), width, height,
+                                    C.byref(p), C.c_void_p(out_ptr), C.c_void_p(stream)), lib)
+
+
+def denoise_tensor(color, features, out=None, **params):
+    """The filter over contiguous fp32 torch tensors on a ROCm device: color (H, W, 3), features
+    (H, W, 8) -> a new (H, W, 3) tensor, or `out` (which may be `color`). The tensors' data_ptr()
+    and torch's current stream go to the library; nothing passes through the host."""
+    import torch
+    if not (color.is_cuda and features.is_cuda and color.device == features.device):
+        raise BDPTError("denoise_tensor: color and features must be on one GPU")
+    if color.dtype != torch.float32 or features.dtype != torch.float32:
+        raise BDPTError("denoise_tensor: fp32 tensors only")
+    if not (color.is_contiguous() and features.is_contiguous()):
+        raise BDPTError("denoise_tensor: contiguous tensors only")
+    if color.dim() != 3 or color.shape[2] != 3 or tuple(features.shape) != (color.shape[0], color.shape[1], 8):
+        raise BDPTError("denoise_tensor: color (H, W, 3) and features (H, W, 8)")
+    if out is None:
+        out = torch.empty_like(color)
+    elif not (out.is_cuda and out.device == color.device and out.dtype == torch.float32 and out.is_contiguous()
+              and out.shape == color.shape):
+        raise BDPTError("denoise_tensor: out must match color")
+    dev = color.device.index if color.device.index is not None else torch.cuda.current_device()
+    denoise_buffers(color.data_ptr(), features.data_ptr(), int(color.shape[1]), int(color.shape[0]),
+                    out.data_ptr(), device=dev, stream=torch.cuda.current_stream(color.device).cuda_stream, **params)
+    return out
 
 
 class BidirectionalPathTracer:
@@ -463,6 +534,51 @@ class BidirectionalPathTracer:
         out = (C.c_int32 * 8)()
         _check(self.lib.bdpt_debug_launch_plan(self.ctx, out), self.lib)
         return dict(zip(("lm", "lstack_on", "ntop", "lds_bytes", "grid", "spl", "nitems", "staged"), list(out)))
+
+    # --- denoised output ---------------------------------------------------------
+    def render_features(self, tiles: Sequence[tuple] = (), spp: int = 0) -> None:
+        """The first-hit feature pass over the tiles (none: the whole frame) with samples [0, spp)
+        of this context's own primary rays (0: all of its spp). Async."""
+        n = len(tiles)
+        arr = (Tile * max(1, n))()
+        for i, t in enumerate(tiles):
+            arr[i] = Tile(*t)
+        _check(self.lib.bdpt_render_features(self.ctx, arr if n else None, n, spp), self.lib)
+
+    def read_features_raw(self) -> np.ndarray:
+        """The feature frame as stored: (H, W, 8) float32 {albedo.rgb, normal.xyz, depth, coverage}."""
+        out = np.empty((self.height, self.width, 8), dtype=np.float32)
+        _check(self.lib.bdpt_read_features(self.ctx, out.ctypes.data_as(C.POINTER(C.c_float))), self.lib)
+        return out
+
+    def read_features(self) -> dict:
+        """albedo (H, W, 3), normal (H, W, 3), depth (H, W), coverage (H, W); row 0 = bottom."""
+        f = self.read_features_raw()
+        return {"albedo": f[..., 0:3].copy(), "normal": f[..., 3:6].copy(), "depth": f[..., 6].copy(),
+                "coverage": f[..., 7].copy()}
+
+    def features_device_ptr(self) -> int:
+        p = C.c_void_p()
+        _check(self.lib.bdpt_features_device_ptr(self.ctx, C.byref(p)), self.lib)
+        return int(p.value or 0)
+
+    def denoise(self, which: int = FRAME_SAMPLE, **params) -> np.ndarray:
+        """Filters frame `which` with this context's features (render_features first) and returns
+        the denoised (H, W, 3) frame. params: levels, sigma_color, sigma_normal, sigma_depth,
+        demodulate (denoise_params)."""
+        p = denoise_params(**params)
+        _check(self.lib.bdpt_denoise(self.ctx, which, C.byref(p)), self.lib)
+        return self.read_denoised()
+
+    def read_denoised(self) -> np.ndarray:
+        out = np.empty((self.height, self.width, 3), dtype=np.float32)
+        _check(self.lib.bdpt_read_denoised(self.ctx, out.ctypes.data_as(C.POINTER(C.c_float))), self.lib)
+        return out
+
+    def denoised_device_ptr(self) -> int:
+        p = C.c_void_p()
+        _check(self.lib.bdpt_denoised_device_ptr(self.ctx, C.byref(p)), self.lib)
+        return int(p.value or 0)
 
     def trace_rays(self, rays: np.ndarray, any_hit: bool = False):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)

@@ -71,6 +71,15 @@ struct Ctx {
   int maxv = 5;
   int ncu = 256;
   size_t npix = 0;
+  // Denoised output (bdpt_denoise.hip), all allocated on first use: the feature
+  // frame (W*H*8), the denoised frame (W*H*3), the filter's two ping-pong frames, and the 8x8 block
+  // list of a tiled feature pass.
+  float* d_features = nullptr;
+  float* d_denoised = nullptr;
+  float* d_dn_scratch = nullptr;
+  int4* d_feat_blocks = nullptr;
+  size_t feat_blocks_cap = 0;
+  bool denoised_valid = false;
 };
 
 #define HIPCHK(x)                                                                   \

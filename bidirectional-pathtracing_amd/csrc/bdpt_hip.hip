@@ -210,7 +210,8 @@ int launch_pt(Ctx* c, PtKParams& kp) {
 void free_ctx(Ctx* c) {
   if (!c) return;
   void* bufs[] = {c->d_nodes2, c->d_nodes4, c->d_geom, c->d_shade, c->d_mats, c->d_lights, c->d_prim_ref, c->d_env, c->d_count, c->d_work8, c->d_leaves,
-                  c->d_eye, c->d_light, c->d_sample, c->d_stats};
+                  c->d_eye, c->d_light, c->d_sample, c->d_stats, c->d_features, c->d_denoised, c->d_dn_scratch,
+                  c->d_feat_blocks};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (Ctx::BlockSlot& b : c->blk) {
@@ -385,6 +386,7 @@ int bdpt_clear(void* ctx) {
   HIPCHK(hipMemsetAsync(c->d_light, 0, fb, c->stream));
   HIPCHK(hipMemsetAsync(c->d_count, 0, c->npix * sizeof(int), c->stream));
   HIPCHK(hipMemsetAsync(c->d_stats, 0, Ctx::kStatSlots * sizeof(unsigned long long), c->stream));
+  if (c->d_features) HIPCHK(hipMemsetAsync(c->d_features, 0, c->npix * 8 * sizeof(float), c->stream));
   return BDPT_OK;
 }
 

@@ -3,7 +3,8 @@
 //
 //   pathtracer [-s spp] [-m max_depth] [-r W H] [-f out.png] [-p x y dx dy] [-t threads] [-c cam.txt]
 //              [-l n] [-e envmap.exr] [--rr] [--infinite-lights] [-g gpus] [-S seed] [--dump-scene scene.json]
-//              [--pt [-a batch tol] [-H] [-b lens] [-d focal]] [--thin-lens [-b lens] [-d focal]] scene.dae
+//              [--pt [-a batch tol] [-H] [-b lens] [-d focal]] [--thin-lens [-b lens] [-d focal]]
+//              [--denoise] [--features] [--denoise-levels n] [--denoise-sigma c n d] [--feature-spp n] scene.dae
 //
 // Same flags and defaults as the reference (-s 1, -m 1, 800x600 when -r is absent; -t / -l are
 // accepted and do not apply to the GPU path; -p renders one cell). -g N splits the sample range
@@ -17,6 +18,10 @@
 // PathTracer's order); without it BDPT is the pinhole whatever -b, -d and -c say.
 // --pt selects the reference's unidirectional PathTracer (pathtracer.cpp:47-340) with its flags
 // -l, -a, -H, -b, -d (main.cpp:107-141); its -g N splits the frame into row bands (whole pixels).
+// --denoise runs the first-hit feature pass and the a-trous filter on the frame after
+// the render (with -g N: on context 0, after the reduce) and writes "<name>_denoised.png" through the
+// same tonemap; --features writes "<name>_albedo.png", "<name>_normal.png" (0.5 n + 0.5) and
+// "<name>_depth.png" (d / max d), linear, clamped, 8-bit. Neither changes the other outputs.
 // Output: the tonemapped PNG and the "_rate.png" sampling-rate image, as render_to_file writes
 // them (raytraced_renderer.cpp:330-347, 690-761). The "Rendering... 100%! (Xs)" time covers the
 // production kernel's render, the frame reduce and the frame read-back; bdpt_create (BVH build + upload) runs before
@@ -61,11 +66,27 @@ void usage(const char* b) {
   printf("  -g  <INT>        Number of GPUs (default 1)\n");
   printf("  --devices <LIST> Device of each of the -g workers, comma-separated (default 0..N-1)\n");
   printf("  -S  <INT>        RNG seed (default 5489)\n");
+  printf("  --denoise        Also write <name>_denoised.png: the frame through the feature-guided a-trous filter\n");
+  printf("  --features       Also write <name>_albedo.png, <name>_normal.png, <name>_depth.png (first-hit features)\n");
+  printf("  --denoise-levels <INT>  Filter levels, 0..8 (default: the library's)\n");
+  printf("  --denoise-sigma <C> <N> <D>  Filter sigmas: colour, normal, depth (default: the library's)\n");
+  printf("  --feature-spp <INT>  Samples per pixel of the feature pass, 1..spp (default: spp)\n");
   printf("  --dump-scene <FILE>  Write the loaded scene as JSON\n");
   printf("  --no-stats       Skip the ray / intersection-test counters of the end-of-render report\n");
   printf("  --tonemap <in.f64> <W> <H> <out.png>  Output stage only: raw float64 RGB (row 0 =\n"
          "                   bottom) -> PNG + _rate.png, as render_to_file writes them\n");
   printf("  -h               Print this help message\n");
+}
+
+// "<name>.png" -> "<name><suffix>.png" (write_rate_png's rule)
+std::string sibling(const std::string& png_path, const char* suffix) {
+  return png_path.size() > 4 ? png_path.substr(0, png_path.size() - 4) + suffix + ".png" : png_path + suffix + ".png";
+}
+
+// Linear, clamped, 8 bits by truncation (ImageBuffer::update_pixel): no tonemap.
+uint32_t pack_linear(float r, float g, float b) {
+  auto c = [](float v) { return (uint32_t)(std::min(std::max(v, 0.f), 1.f) * 255); };
+  return c(r) | (c(g) << 8) | (c(b) << 16);
 }
 
 int fail(const char* what) {
@@ -82,6 +103,9 @@ int main(int argc, char** argv) {
   std::string out, dump, scene, envpath, cam_settings;
   std::vector<int> devices;
   bool rr = false, pt = false, hemi = false, stats = true, inf_lights = false, thin_lens = false;
+  bool denoise = false, features = false;
+  int dn_levels = -1, feature_spp = 0;
+  float dn_sigma[3] = {0, 0, 0};
   int nal = 1, batch = 32;
   float tol = 0.05f;
   double lens = 0.0, focal = 4.7;
@@ -120,6 +144,11 @@ int main(int argc, char** argv) {
     else if (a == "--infinite-lights") inf_lights = true;
     else if (a == "--thin-lens") thin_lens = true;
     else if (a == "--no-stats") stats = false;
+    else if (a == "--denoise") denoise = true;
+    else if (a == "--features") features = true;
+    else if (a == "--denoise-levels") { need(1); dn_levels = atoi(argv[++i]); }
+    else if (a == "--denoise-sigma") { need(3); for (int k = 0; k < 3; k++) dn_sigma[k] = (float)atof(argv[i + 1 + k]); i += 3; }
+    else if (a == "--feature-spp") { need(1); feature_spp = atoi(argv[++i]); }
     else if (a == "--tonemap") {
       need(4);
       const int tw = atoi(argv[i + 2]), tht = atoi(argv[i + 3]);
@@ -283,6 +312,34 @@ int main(int argc, char** argv) {
     return 1;
   }
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  // --denoise / --features: the feature pass and the filter on context 0, which holds the whole
+  // frame (after the reduce with -g N); outside the render's timer
+  std::vector<float> feat, den;
+  if (denoise || features) {
+    feat.resize((size_t)w * h * 8);
+    const auto tf = std::chrono::steady_clock::now();
+    if (bdpt_render_features(ctxs[0], nullptr, 0, feature_spp) != BDPT_OK || bdpt_read_features(ctxs[0], feat.data()) != BDPT_OK) {
+      fail("rendering the features");
+      cleanup();
+      return 1;
+    }
+    if (denoise) {
+      bdpt_denoise_params dp;
+      bdpt_denoise_default_params(&dp);
+      if (dn_levels >= 0) dp.levels = dn_levels;
+      if (dn_sigma[0] != 0 || dn_sigma[1] != 0 || dn_sigma[2] != 0) {
+        dp.sigma_color = dn_sigma[0]; dp.sigma_normal = dn_sigma[1]; dp.sigma_depth = dn_sigma[2];
+      }
+      den.resize((size_t)w * h * 3);
+      if (bdpt_denoise(ctxs[0], BDPT_FRAME_SAMPLE, &dp) != BDPT_OK || bdpt_read_denoised(ctxs[0], den.data()) != BDPT_OK) {
+        fail("denoising");
+        cleanup();
+        return 1;
+      }
+    }
+    fprintf(stderr, "[PathTracer] features%s: %.4fs\n", denoise ? " + denoise" : "",
+            std::chrono::duration<double>(std::chrono::steady_clock::now() - tf).count());
+  }
   release();
   if (stats && !run(2)) { cleanup(); return 1; }
   const double samples = (double)(tiles.empty() ? (long long)w * h : cdx * cdy) * spp;
@@ -328,6 +385,25 @@ int main(int argc, char** argv) {
       for (long x = std::max(0L, cx); x < std::min((long)w, cx + cdx); x++) rate[(size_t)y * w + x] = 1.0f;
   }
   bdpt::write_rate_png(out, rate, w, h);
+  if (denoise) {
+    const std::vector<double> dh(den.begin(), den.end());
+    if (!bdpt::write_png(sibling(out, "_denoised"), bdpt::tonemap(dh.data(), w, h), w, h)) { fprintf(stderr, "[PathTracer] cannot write the denoised image\n"); return 1; }
+  }
+  if (features) {
+    const size_t n = (size_t)w * h;
+    float dmax = 0.0f;
+    for (size_t k = 0; k < n; k++) dmax = std::max(dmax, feat[8 * k + 6]);
+    std::vector<uint32_t> alb(n), nrm(n), dep(n);
+    for (size_t k = 0; k < n; k++) {
+      const float* f = &feat[8 * k];
+      alb[k] = pack_linear(f[0], f[1], f[2]);
+      nrm[k] = pack_linear(0.5f * f[3] + 0.5f, 0.5f * f[4] + 0.5f, 0.5f * f[5] + 0.5f);
+      const float d = dmax > 0 ? f[6] / dmax : 0.0f;
+      dep[k] = pack_linear(d, d, d);
+    }
+    if (!bdpt::write_png(sibling(out, "_albedo"), alb, w, h) || !bdpt::write_png(sibling(out, "_normal"), nrm, w, h) ||
+        !bdpt::write_png(sibling(out, "_depth"), dep, w, h)) { fprintf(stderr, "[PathTracer] cannot write the feature images\n"); return 1; }
+  }
   fprintf(stdout, "[PathTracer] Job completed.\n");
   cleanup();
   return 0;

@@ -39,6 +39,9 @@
  *     environment light's machinery: bdpt_params.infinite_lights. At most
  *     one light that an escaped ray can reach — the environment map or one ambient light — per
  *     scene; any number of directional lights.
+ * Denoised output (new symbols only, the ABI version is unchanged): per-pixel first-hit
+ * feature buffers through the integrator's own primary rays (bdpt_render_features) and a
+ * feature-guided edge-avoiding a-trous filter over a frame (bdpt_denoise, bdpt_denoise_buffers).
  * And the reference's second integrator: the unidirectional PathTracer
  * (pathtracer.cpp:47-340 — NEE, adaptive sampling, thin lens, roulette at -m 0, the environment
  * light, MicrofacetBSDF), selected by bdpt_params.integrator = BDPT_INTEGRATOR_PT (ABI v3).
@@ -299,6 +302,61 @@ int bdpt_debug_lane_counters(void* ctx, uint64_t* out16);
  * materials and lights to LDS (0: it reads them from global memory)}. -1: no launch yet, or not
  * applicable to the PathTracer's kernel. Touches no device. */
 int bdpt_debug_launch_plan(void* ctx, int32_t* out8);
+
+/* Denoised output. New symbols only: no struct above changes and the ABI version
+ * stays 10. A context that never calls them allocates nothing and runs nothing for them.
+ *
+ * The feature pass: per pixel 8 interleaved floats {albedo.rgb, normal.xyz, depth, coverage} of the
+ * first hit of the context's integrator's own primary rays (the same origin, direction and clip
+ * window as the first closest-hit query of every eye path at the context's seed, lens included), a
+ * W*H*8 float frame, row 0 = bottom. Albedo and normal are means over the samples (a miss adds
+ * zeros; the normal faces the ray and is not renormalised), depth is the mean hit distance over the
+ * samples that hit, coverage the fraction that hit. Albedo by material: diffuse and mirror a,
+ * refraction b, glass max(a, b), emission min(a, 1), microfacet its Fresnel reflectance at normal
+ * incidence. Deterministic: one lane owns a pixel and sums in sample order.
+ *
+ * bdpt_render_features renders samples [0, spp_count) (0 = the ctx's spp; otherwise
+ * 1 <= spp_count <= spp) of the pixels of the tiles (clipped as bdpt_render clips them; ntiles == 0:
+ * the whole frame), overwriting their records. It allocates the feature frame on first use and
+ * leaves the eye / light / sample frames, the sample counts and bdpt_stats alone. Async on the ctx
+ * stream (a tile list is uploaded after the stream's earlier work has finished). bdpt_clear zeroes
+ * the feature frame once it exists. */
+int bdpt_render_features(void* ctx, const bdpt_tile* tiles, int32_t ntiles, int32_t spp_count);
+/* The feature frame as W*H*8 floats (sync). BDPT_E_INVALID before the first feature pass. */
+int bdpt_read_features(void* ctx, float* out8);
+int bdpt_features_device_ptr(void* ctx, void** dptr);
+
+/* The edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) of a W*H*3 colour frame C guided
+ * by a feature frame: `levels` passes, pass i over the 5x5 taps q = p + 2^i (dx, dy) inside the frame
+ * with the B3 kernel h = k[dx] k[dy], k = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *   c_{i+1}(p) = sum_q h w(p, q) c_i(q) / sum_q h w(p, q),   w = expf(-(e_c + e_n + e_d)),
+ *   e_c = |c_i(p) - c_i(q)|^2 / (sigma_color 2^-i)^2,  e_n = |n(p) - n(q)|^2 / sigma_normal^2,
+ *   e_d = ((d(p) - d(q)) / (sigma_depth max(d(p), d(q))))^2 (0 where both depths are 0),
+ * the centre tap's w = 1. demodulate: c_0 = C / (albedo + 0.01), out = c_L (albedo + 0.01); off:
+ * c_0 = C, out = c_L. levels = 0 with demodulate off returns the input bit for bit.
+ * A NULL bdpt_denoise_params pointer means the defaults. levels 0..8, sigmas > 0,
+ * reserved words 0. */
+typedef struct bdpt_denoise_params {
+  int32_t levels;
+  float sigma_color, sigma_normal, sigma_depth;
+  int32_t demodulate;
+  int32_t reserved[3];
+} bdpt_denoise_params;
+/* Fills *p with the defaults. */
+int bdpt_denoise_default_params(bdpt_denoise_params* p);
+/* Filters frame `which` (BDPT_FRAME_SAMPLE = eye + light under BDPT) with the ctx's feature frame
+ * into the ctx's denoised frame (allocated on first use). Async. BDPT_E_INVALID before the first
+ * feature pass. */
+int bdpt_denoise(void* ctx, int32_t which, const bdpt_denoise_params* p);
+/* The denoised frame, W*H*3 floats, row 0 = bottom (sync). BDPT_E_INVALID before bdpt_denoise. */
+int bdpt_read_denoised(void* ctx, float* rgb);
+int bdpt_denoised_device_ptr(void* ctx, void** dptr);
+/* The same filter on caller device memory of `device`, without a ctx: d_color w*h*3 floats,
+ * d_features w*h*8 floats (16-byte aligned), d_out w*h*3 floats (may equal d_color), enqueued on
+ * `stream` (a hipStream_t; NULL = the null stream). It allocates its two scratch frames and frees
+ * them once the stream has run the filter, so it returns after the result is in d_out. */
+int bdpt_denoise_buffers(int32_t device, const float* d_color, const float* d_features, int32_t w, int32_t h,
+                         const bdpt_denoise_params* p, float* d_out, void* stream);
 
 /* Host-side COLLADA loader: the reference CLI's scene path (ColladaParser::load,
  * collada.cpp:129-941, + Application::load, application.cpp:228-304). width/height > 0 apply
