@@ -86,6 +86,13 @@ class DenoiseParams(C.Structure):
                 ("sigma_depth", C.c_float), ("demodulate", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class DenoiseVarianceParams(C.Structure):
+    """bdpt_denoise_variance_params: the variance-guided a-trous filter's settings.
+    denoise_variance_params() fills the library's defaults."""
+    _fields_ = [("levels", C.c_int32), ("sigma_variance", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
 class Tile(C.Structure):
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
 
@@ -359,6 +366,17 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.bdpt_denoised_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     lib.bdpt_denoise_buffers.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                          C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p]
+    lib.bdpt_render_batches.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+    lib.bdpt_variance.argtypes = [C.c_void_p]
+    lib.bdpt_read_variance.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    lib.bdpt_variance_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.bdpt_read_moments.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    lib.bdpt_denoise_variance_default_params.argtypes = [C.POINTER(DenoiseVarianceParams)]
+    lib.bdpt_denoise_variance.argtypes = [C.c_void_p, C.POINTER(DenoiseVarianceParams)]
+    lib.bdpt_moments_buffers.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.bdpt_variance_buffers.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.bdpt_denoise_variance_buffers.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                  C.POINTER(DenoiseVarianceParams), C.c_void_p, C.c_void_p, C.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -427,6 +445,82 @@ def denoise_tensor(color, features, out=None, **params):
     denoise_buffers(color.data_ptr(), features.data_ptr(), int(color.shape[1]), int(color.shape[0]),
                     out.data_ptr(), device=dev, stream=torch.cuda.current_stream(color.device).cuda_stream, **params)
     return out
+
+
+def denoise_variance_params(levels: Optional[int] = None, sigma_variance: Optional[float] = None,
+                            sigma_normal: Optional[float] = None,
+                            sigma_depth: Optional[float] = None) -> DenoiseVarianceParams:
+    """The library's default settings of the variance-guided filter
+    (bdpt_denoise_variance_default_params) with the given ones replaced."""
+    lib = load_library()
+    p = DenoiseVarianceParams()
+    _check(lib.bdpt_denoise_variance_default_params(C.byref(p)), lib)
+    if levels is not None:
+        p.levels = levels
+    if sigma_variance is not None:
+        p.sigma_variance = sigma_variance
+    if sigma_normal is not None:
+        p.sigma_normal = sigma_normal
+    if sigma_depth is not None:
+        p.sigma_depth = sigma_depth
+    return p
+
+
+def moments_buffers(frame_a_ptr: int, frame_b_ptr: int, record_ptr: int, width: int, height: int,
+                    device: int = 0, stream: int = 0) -> None:
+    """bdpt_moments_buffers: one batch into the W*H*4 record; the cumulative frame is frame_a, or
+    frame_a + frame_b when frame_b_ptr is not 0 (W*H*3 floats each). Async on `stream`."""
+    lib = load_library()
+    _check(lib.bdpt_moments_buffers(device, C.c_void_p(frame_a_ptr), C.c_void_p(frame_b_ptr or None),
+                                    C.c_void_p(record_ptr), width, height, C.c_void_p(stream)), lib)
+
+
+def variance_buffers(record_ptr: int, batches: int, width: int, height: int, var_ptr: int,
+                     device: int = 0, stream: int = 0) -> None:
+    """bdpt_variance_buffers: the W*H variance frame of a record of `batches` batches. Async."""
+    lib = load_library()
+    _check(lib.bdpt_variance_buffers(device, C.c_void_p(record_ptr), batches, width, height, C.c_void_p(var_ptr),
+                                     C.c_void_p(stream)), lib)
+
+
+def denoise_variance_buffers(color_ptr: int, var_ptr: int, features_ptr: int, width: int, height: int, out_ptr: int,
+                             var_out_ptr: int = 0, device: int = 0, stream: int = 0, **params) -> None:
+    """bdpt_denoise_variance_buffers: the variance-guided filter over raw device pointers (color
+    W*H*3, var W*H, features W*H*8, out W*H*3, which may be the colour buffer; var_out W*H or 0)."""
+    lib = load_library()
+    p = denoise_variance_params(**params)
+    _check(lib.bdpt_denoise_variance_buffers(device, C.c_void_p(color_ptr), C.c_void_p(var_ptr),
+                                             C.c_void_p(features_ptr), width, height, C.byref(p), C.c_void_p(out_ptr),
+                                             C.c_void_p(var_out_ptr or None), C.c_void_p(stream)), lib)
+
+
+def denoise_variance_tensor(color, var, features, out=None, var_out=None, **params):
+    """The variance-guided filter over contiguous fp32 torch tensors on a ROCm device: color
+    (H, W, 3), var (H, W), features (H, W, 8) -> (colour, variance): new tensors, or `out` (which may
+    be `color`) and `var_out` (which may be `var`). The tensors' data_ptr() and torch's current
+    stream go to the library; nothing passes through the host."""
+    import torch
+    ts = (color, var, features)
+    if not all(t.is_cuda and t.device == color.device for t in ts):
+        raise BDPTError("denoise_variance_tensor: color, var and features must be on one GPU")
+    if not all(t.dtype == torch.float32 and t.is_contiguous() for t in ts):
+        raise BDPTError("denoise_variance_tensor: contiguous fp32 tensors only")
+    if color.dim() != 3 or color.shape[2] != 3 or tuple(var.shape) != tuple(color.shape[:2]) or \
+            tuple(features.shape) != (color.shape[0], color.shape[1], 8):
+        raise BDPTError("denoise_variance_tensor: color (H, W, 3), var (H, W) and features (H, W, 8)")
+    if out is None:
+        out = torch.empty_like(color)
+    if var_out is None:
+        var_out = torch.empty_like(var)
+    for t, like, name in ((out, color, "out"), (var_out, var, "var_out")):
+        if not (t.is_cuda and t.device == color.device and t.dtype == torch.float32 and t.is_contiguous()
+                and t.shape == like.shape):
+            raise BDPTError(f"denoise_variance_tensor: {name} must match its input")
+    dev = color.device.index if color.device.index is not None else torch.cuda.current_device()
+    denoise_variance_buffers(color.data_ptr(), var.data_ptr(), features.data_ptr(), int(color.shape[1]),
+                             int(color.shape[0]), out.data_ptr(), var_out.data_ptr(), device=dev,
+                             stream=torch.cuda.current_stream(color.device).cuda_stream, **params)
+    return out, var_out
 
 
 class BidirectionalPathTracer:
@@ -579,6 +673,42 @@ class BidirectionalPathTracer:
         p = C.c_void_p()
         _check(self.lib.bdpt_denoised_device_ptr(self.ctx, C.byref(p)), self.lib)
         return int(p.value or 0)
+
+    # --- variance-guided denoise -------------------------------------------------
+    def render_batches(self, spp_begin: int = 0, spp_count: Optional[int] = None, batches: int = 4) -> None:
+        """Renders samples [spp_begin, spp_begin + spp_count) of the whole frame as `batches` equal
+        ranges and keeps their per-pixel moments (spp_count None: up to this context's spp). Async."""
+        cnt = self.spp - spp_begin if spp_count is None else spp_count
+        _check(self.lib.bdpt_render_batches(self.ctx, spp_begin, cnt, batches), self.lib)
+
+    def variance(self) -> None:
+        """Computes the variance frame from the batch moments (render_batches first). Async."""
+        _check(self.lib.bdpt_variance(self.ctx), self.lib)
+
+    def read_variance(self) -> np.ndarray:
+        """The variance frame: (H, W) float32, the trace of the covariance of each pixel's colour."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        _check(self.lib.bdpt_read_variance(self.ctx, out.ctypes.data_as(C.POINTER(C.c_float))), self.lib)
+        return out
+
+    def variance_device_ptr(self) -> int:
+        p = C.c_void_p()
+        _check(self.lib.bdpt_variance_device_ptr(self.ctx, C.byref(p)), self.lib)
+        return int(p.value or 0)
+
+    def read_moments(self) -> np.ndarray:
+        """The moments record as stored: (H, W, 4) float32 {prev.r, prev.g, prev.b, Q}."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        _check(self.lib.bdpt_read_moments(self.ctx, out.ctypes.data_as(C.POINTER(C.c_float))), self.lib)
+        return out
+
+    def denoise_variance(self, **params) -> np.ndarray:
+        """Filters the sample frame with this context's variance and features (render_batches,
+        variance and render_features first) and returns the denoised (H, W, 3) frame. params:
+        levels, sigma_variance, sigma_normal, sigma_depth (denoise_variance_params)."""
+        p = denoise_variance_params(**params)
+        _check(self.lib.bdpt_denoise_variance(self.ctx, C.byref(p)), self.lib)
+        return self.read_denoised()
 
     def trace_rays(self, rays: np.ndarray, any_hit: bool = False):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)

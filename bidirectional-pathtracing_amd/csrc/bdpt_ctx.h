@@ -80,6 +80,16 @@ struct Ctx {
   int4* d_feat_blocks = nullptr;
   size_t feat_blocks_cap = 0;
   bool denoised_valid = false;
+  // Variance-guided denoise (bdpt_variance.hip), all allocated on first use: the
+  // moments record (W*H float4 {prev.rgb, Q}), the variance frame (W*H) and the filter's two
+  // variance ping-pong frames. var_batches: batches in the record (K); var_batch_spp: samples per
+  // batch; var_unbatched: bdpt_render ran outside bdpt_render_batches since the last bdpt_clear;
+  // in_batches: bdpt_render_batches is the caller of bdpt_render.
+  float* d_moments = nullptr;
+  float* d_variance = nullptr;
+  float* d_var_scratch = nullptr;
+  int var_batches = 0, var_batch_spp = 0;
+  bool var_unbatched = false, in_batches = false, variance_valid = false;
 };
 
 #define HIPCHK(x)                                                                   \

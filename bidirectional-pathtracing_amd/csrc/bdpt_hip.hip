@@ -211,7 +211,7 @@ void free_ctx(Ctx* c) {
   if (!c) return;
   void* bufs[] = {c->d_nodes2, c->d_nodes4, c->d_geom, c->d_shade, c->d_mats, c->d_lights, c->d_prim_ref, c->d_env, c->d_count, c->d_work8, c->d_leaves,
                   c->d_eye, c->d_light, c->d_sample, c->d_stats, c->d_features, c->d_denoised, c->d_dn_scratch,
-                  c->d_feat_blocks};
+                  c->d_feat_blocks, c->d_moments, c->d_variance, c->d_var_scratch};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (Ctx::BlockSlot& b : c->blk) {
@@ -387,6 +387,10 @@ int bdpt_clear(void* ctx) {
   HIPCHK(hipMemsetAsync(c->d_count, 0, c->npix * sizeof(int), c->stream));
   HIPCHK(hipMemsetAsync(c->d_stats, 0, Ctx::kStatSlots * sizeof(unsigned long long), c->stream));
   if (c->d_features) HIPCHK(hipMemsetAsync(c->d_features, 0, c->npix * 8 * sizeof(float), c->stream));
+  // the batch moments (bdpt_variance.hip) start over with the frame
+  if (c->d_moments) HIPCHK(hipMemsetAsync(c->d_moments, 0, c->npix * 4 * sizeof(float), c->stream));
+  c->var_batches = c->var_batch_spp = 0;
+  c->var_unbatched = c->variance_valid = false;
   return BDPT_OK;
 }
 
@@ -397,6 +401,7 @@ int bdpt_render(void* ctx, const bdpt_tile* tiles, int32_t ntiles, int32_t spp_b
   if ((int64_t)spp_begin + spp_count > INT32_MAX) { g_err = "spp_begin + spp_count overflows int32"; return BDPT_E_INVALID; }
   if (spp_count == 0) return BDPT_OK;
   std::lock_guard<std::recursive_mutex> lk(c->mu);
+  if (!c->in_batches) c->var_unbatched = true;   // samples outside bdpt_render_batches: no variance of this frame
   HIPCHK(hipSetDevice(c->device));
   const int W = c->prm.width, H = c->prm.height;
   KParams kp;

@@ -4,7 +4,8 @@
 //   pathtracer [-s spp] [-m max_depth] [-r W H] [-f out.png] [-p x y dx dy] [-t threads] [-c cam.txt]
 //              [-l n] [-e envmap.exr] [--rr] [--infinite-lights] [-g gpus] [-S seed] [--dump-scene scene.json]
 //              [--pt [-a batch tol] [-H] [-b lens] [-d focal]] [--thin-lens [-b lens] [-d focal]]
-//              [--denoise] [--features] [--denoise-levels n] [--denoise-sigma c n d] [--feature-spp n] scene.dae
+//              [--denoise] [--features] [--denoise-levels n] [--denoise-sigma c n d] [--feature-spp n]
+//              [--denoise-batches k] [--denoise-sigma-variance v] scene.dae
 //
 // Same flags and defaults as the reference (-s 1, -m 1, 800x600 when -r is absent; -t / -l are
 // accepted and do not apply to the GPU path; -p renders one cell). -g N splits the sample range
@@ -22,6 +23,11 @@
 // the render (with -g N: on context 0, after the reduce) and writes "<name>_denoised.png" through the
 // same tonemap; --features writes "<name>_albedo.png", "<name>_normal.png" (0.5 n + 0.5) and
 // "<name>_depth.png" (d / max d), linear, clamped, 8-bit. Neither changes the other outputs.
+// --denoise-batches K (BDPT, one GPU, whole frame, K >= 2 dividing -s) renders the frame as K equal
+// sample batches and keeps their per-pixel moments (bdpt_render_batches); --denoise is
+// then the variance-guided filter (--denoise-sigma-variance overrides its sigma_variance,
+// --denoise-levels its levels, --denoise-sigma's N and D its other two sigmas), and --features also
+// writes "<name>_stderr.png": the pixel's standard error sqrt(v) as a grey through the tonemap.
 // Output: the tonemapped PNG and the "_rate.png" sampling-rate image, as render_to_file writes
 // them (raytraced_renderer.cpp:330-347, 690-761). The "Rendering... 100%! (Xs)" time covers the
 // production kernel's render, the frame reduce and the frame read-back; bdpt_create (BVH build + upload) runs before
@@ -30,6 +36,7 @@
 // skips it).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -71,6 +78,10 @@ void usage(const char* b) {
   printf("  --denoise-levels <INT>  Filter levels, 0..8 (default: the library's)\n");
   printf("  --denoise-sigma <C> <N> <D>  Filter sigmas: colour, normal, depth (default: the library's)\n");
   printf("  --feature-spp <INT>  Samples per pixel of the feature pass, 1..spp (default: spp)\n");
+  printf("  --denoise-batches <INT>  Render as K equal sample batches (BDPT, -g 1, no -p; K >= 2 divides -s) and keep\n"
+         "                   their per-pixel variance: --denoise becomes the variance-guided filter, --features\n"
+         "                   also writes <name>_stderr.png (the standard error through the tonemap)\n");
+  printf("  --denoise-sigma-variance <V>  Variance-guided filter: sigma_variance (default: the library's)\n");
   printf("  --dump-scene <FILE>  Write the loaded scene as JSON\n");
   printf("  --no-stats       Skip the ray / intersection-test counters of the end-of-render report\n");
   printf("  --tonemap <in.f64> <W> <H> <out.png>  Output stage only: raw float64 RGB (row 0 =\n"
@@ -104,7 +115,8 @@ int main(int argc, char** argv) {
   std::vector<int> devices;
   bool rr = false, pt = false, hemi = false, stats = true, inf_lights = false, thin_lens = false;
   bool denoise = false, features = false;
-  int dn_levels = -1, feature_spp = 0;
+  int dn_levels = -1, feature_spp = 0, dn_batches = 0;
+  float dn_sigma_var = 0;
   float dn_sigma[3] = {0, 0, 0};
   int nal = 1, batch = 32;
   float tol = 0.05f;
@@ -149,6 +161,8 @@ int main(int argc, char** argv) {
     else if (a == "--denoise-levels") { need(1); dn_levels = atoi(argv[++i]); }
     else if (a == "--denoise-sigma") { need(3); for (int k = 0; k < 3; k++) dn_sigma[k] = (float)atof(argv[i + 1 + k]); i += 3; }
     else if (a == "--feature-spp") { need(1); feature_spp = atoi(argv[++i]); }
+    else if (a == "--denoise-batches") { need(1); dn_batches = atoi(argv[++i]); }
+    else if (a == "--denoise-sigma-variance") { need(1); dn_sigma_var = (float)atof(argv[++i]); }
     else if (a == "--tonemap") {
       need(4);
       const int tw = atoi(argv[i + 2]), tht = atoi(argv[i + 3]);
@@ -168,6 +182,10 @@ int main(int argc, char** argv) {
     else scene = a;
   }
   if (scene.empty() || gpus < 1) { usage(argv[0]); return 1; }
+  if (dn_batches != 0 && (dn_batches < 2 || spp % dn_batches != 0 || pt || gpus != 1 || cx >= 0)) {
+    fprintf(stderr, "[PathTracer] --denoise-batches K: K >= 2 must divide -s, under BDPT, with -g 1 and without -p\n");
+    return 1;
+  }
   fprintf(stderr, "[PathTracer] Input scene file: %s\n", scene.c_str());
   bdpt_dae* dae = nullptr;
   if (bdpt_dae_load(scene.c_str(), w, h, &dae) != BDPT_OK) return fail("loading scene");
@@ -249,7 +267,9 @@ int main(int argc, char** argv) {
           bdpt_params p = params(g, false);
           rc = bdpt_create(&desc, &p, &ctxs[g]);
         } else if (phase == 1) {
-          if (s1[g] > s0[g])
+          if (s1[g] > s0[g] && dn_batches > 0)
+            rc = bdpt_render_batches(ctxs[g], s0[g], s1[g] - s0[g], dn_batches);
+          else if (s1[g] > s0[g])
             rc = bdpt_render(ctxs[g], mine[g].empty() ? nullptr : mine[g].data(), (int32_t)mine[g].size(), s0[g], s1[g] - s0[g]);
         } else {
           bdpt_params p = params(g, true);
@@ -314,7 +334,15 @@ int main(int argc, char** argv) {
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   // --denoise / --features: the feature pass and the filter on context 0, which holds the whole
   // frame (after the reduce with -g N); outside the render's timer
-  std::vector<float> feat, den;
+  std::vector<float> feat, den, var;
+  if (dn_batches > 0 && (denoise || features)) {
+    var.resize((size_t)w * h);
+    if (bdpt_variance(ctxs[0]) != BDPT_OK || bdpt_read_variance(ctxs[0], var.data()) != BDPT_OK) {
+      fail("computing the variance");
+      cleanup();
+      return 1;
+    }
+  }
   if (denoise || features) {
     feat.resize((size_t)w * h * 8);
     const auto tf = std::chrono::steady_clock::now();
@@ -323,7 +351,19 @@ int main(int argc, char** argv) {
       cleanup();
       return 1;
     }
-    if (denoise) {
+    if (denoise && dn_batches > 0) {
+      bdpt_denoise_variance_params vp;
+      bdpt_denoise_variance_default_params(&vp);
+      if (dn_levels >= 0) vp.levels = dn_levels;
+      if (dn_sigma_var != 0) vp.sigma_variance = dn_sigma_var;
+      if (dn_sigma[0] != 0 || dn_sigma[1] != 0 || dn_sigma[2] != 0) { vp.sigma_normal = dn_sigma[1]; vp.sigma_depth = dn_sigma[2]; }
+      den.resize((size_t)w * h * 3);
+      if (bdpt_denoise_variance(ctxs[0], &vp) != BDPT_OK || bdpt_read_denoised(ctxs[0], den.data()) != BDPT_OK) {
+        fail("denoising");
+        cleanup();
+        return 1;
+      }
+    } else if (denoise) {
       bdpt_denoise_params dp;
       bdpt_denoise_default_params(&dp);
       if (dn_levels >= 0) dp.levels = dn_levels;
@@ -400,6 +440,11 @@ int main(int argc, char** argv) {
       nrm[k] = pack_linear(0.5f * f[3] + 0.5f, 0.5f * f[4] + 0.5f, 0.5f * f[5] + 0.5f);
       const float d = dmax > 0 ? f[6] / dmax : 0.0f;
       dep[k] = pack_linear(d, d, d);
+    }
+    if (!var.empty()) {   // the standard error as a grey, through the beauty's tonemap
+      std::vector<double> se(n * 3);
+      for (size_t k = 0; k < n; k++) se[3 * k] = se[3 * k + 1] = se[3 * k + 2] = std::sqrt((double)var[k]);
+      if (!bdpt::write_png(sibling(out, "_stderr"), bdpt::tonemap(se.data(), w, h), w, h)) { fprintf(stderr, "[PathTracer] cannot write the standard-error image\n"); return 1; }
     }
     if (!bdpt::write_png(sibling(out, "_albedo"), alb, w, h) || !bdpt::write_png(sibling(out, "_normal"), nrm, w, h) ||
         !bdpt::write_png(sibling(out, "_depth"), dep, w, h)) { fprintf(stderr, "[PathTracer] cannot write the feature images\n"); return 1; }

@@ -42,6 +42,9 @@
  * Denoised output (new symbols only, the ABI version is unchanged): per-pixel first-hit
  * feature buffers through the integrator's own primary rays (bdpt_render_features) and a
  * feature-guided edge-avoiding a-trous filter over a frame (bdpt_denoise, bdpt_denoise_buffers).
+ * Variance-guided denoise (new symbols only as well): a frame rendered in equal sample
+ * batches keeps per-pixel moments (bdpt_render_batches), which give its per-pixel variance
+ * (bdpt_variance) and guide the filter's colour weight (bdpt_denoise_variance, *_buffers).
  * And the reference's second integrator: the unidirectional PathTracer
  * (pathtracer.cpp:47-340 — NEE, adaptive sampling, thin lens, roulette at -m 0, the environment
  * light, MicrofacetBSDF), selected by bdpt_params.integrator = BDPT_INTEGRATOR_PT (ABI v3).
@@ -357,6 +360,72 @@ int bdpt_denoised_device_ptr(void* ctx, void** dptr);
  * them once the stream has run the filter, so it returns after the result is in d_out. */
 int bdpt_denoise_buffers(int32_t device, const float* d_color, const float* d_features, int32_t w, int32_t h,
                          const bdpt_denoise_params* p, float* d_out, void* stream);
+
+/* Variance-guided denoise. New symbols only: no struct above changes and the ABI
+ * version stays 10. A context that never calls them allocates nothing and runs nothing for them.
+ *
+ * Batch moments. A frame rendered as K equal sample batches is the sum of the batches' increments
+ * b_k (the 1/spp weight is per sample; disjoint sample ranges are independent). The moments record
+ * keeps per pixel one float4 {prev.r, prev.g, prev.b, Q}: after each batch, with f the cumulative
+ * colour (under BDPT eye + light, added as BDPT_FRAME_SAMPLE adds them), b = f - prev,
+ * Q += (b.x^2 + b.y^2) + b.z^2, prev = f. The variance frame, one float per pixel, W*H floats, row 0
+ * = bottom, with 1/K and K/(K-1) rounded to fp32 once:
+ *   v = max(0, (Q - ((prev.x^2 + prev.y^2) + prev.z^2) (1/K)) K/(K-1)),
+ * the trace of the covariance of the pixel's colour as rendered (the quantity |dc|^2 compares
+ * with); an unbiased estimate of the frame's variance when the batches are equal. sqrt(v) is the
+ * standard error of the pixel.
+ *
+ * bdpt_render_batches renders samples [spp_begin, spp_begin + spp_count) of the whole frame as
+ * `batches` equal ranges: bdpt_render and a moments pass, `batches` times. batches >= 2,
+ * spp_count > 0 and a multiple of batches; a later call adds further batches and must use the same
+ * samples per batch. BDPT_E_UNSUPPORTED under the PathTracer (it renders whole pixels; its moments
+ * live inside its kernel). Async. bdpt_clear zeroes the record and the batch count. A bdpt_render
+ * outside this call marks the frame: bdpt_variance then returns BDPT_E_INVALID until bdpt_clear. */
+int bdpt_render_batches(void* ctx, int32_t spp_begin, int32_t spp_count, int32_t batches);
+/* Computes the variance frame from the record (allocated on first use). Async. BDPT_E_INVALID with
+ * fewer than 2 batches in the record, or when the frame holds samples not rendered in batches. */
+int bdpt_variance(void* ctx);
+/* The variance frame, W*H floats (sync). BDPT_E_INVALID before bdpt_variance. */
+int bdpt_read_variance(void* ctx, float* var);
+int bdpt_variance_device_ptr(void* ctx, void** dptr);
+/* The raw record, W*H*4 floats (sync). BDPT_E_INVALID before the first bdpt_render_batches. */
+int bdpt_read_moments(void* ctx, float* rec4);
+
+/* The variance-guided a-trous filter (after Schied et al. 2017) of a colour frame C with variance
+ * frame V: bdpt_denoise's taps, kernel h, in-frame rule, e_n and e_d; per level i
+ *   v~(p) = the 3x3 Gaussian (1/4, 1/2, 1/4)^2 of v_i at unit distance around p, in-frame taps only,
+ *           divided by the sum of the weights used,
+ *   e_c = |c_i(p) - c_i(q)|^2 / (sigma_variance^2 v~(p) + 1e-8),  w = expf(-((e_c + e_n) + e_d)),
+ *   c_{i+1}(p) = sum_q h w c_i(q) / sum_q h w   (evaluated as c_i(p) + sum h w (c_i(q) - c_i(p)) / sum h w),
+ *   v_{i+1}(p) = sum_q (h w)^2 v_i(q) / (sum_q h w)^2   (and not above the largest v_i(q) of the taps),
+ * the centre tap's w = 1. sigma_variance is the same at every level: the variance shrinks instead.
+ * No demodulation. levels = 0 returns colour and variance bit for bit.
+ * A NULL params pointer means the defaults. levels 0..8, sigmas > 0, reserved 0. */
+typedef struct bdpt_denoise_variance_params {
+  int32_t levels;
+  float sigma_variance, sigma_normal, sigma_depth;
+  int32_t reserved[4];
+} bdpt_denoise_variance_params;
+/* Fills *p with the defaults. */
+int bdpt_denoise_variance_default_params(bdpt_denoise_variance_params* p);
+/* Filters BDPT_FRAME_SAMPLE with the ctx's variance and feature frames into the ctx's denoised
+ * frame (bdpt_read_denoised). Async. BDPT_E_INVALID before a feature pass or before bdpt_variance. */
+int bdpt_denoise_variance(void* ctx, const bdpt_denoise_variance_params* p);
+/* The same three passes on caller device memory of `device`, without a ctx, enqueued on `stream`
+ * (a hipStream_t; NULL = the null stream). d_record w*h*4 floats and d_features w*h*8 floats are
+ * 16-byte aligned. bdpt_moments_buffers adds one batch to d_record (zero it before the first):
+ * the cumulative frame is d_frame_a, or d_frame_a + d_frame_b when d_frame_b is not NULL (w*h*3
+ * floats each); async. bdpt_variance_buffers writes w*h floats to d_var; async.
+ * bdpt_denoise_variance_buffers filters d_color (w*h*3) with d_var (w*h) into d_out (may equal
+ * d_color) and, when d_var_out is not NULL, the filtered variance into it (may equal d_var); it
+ * allocates its scratch frames and returns after the result is in place. */
+int bdpt_moments_buffers(int32_t device, const float* d_frame_a, const float* d_frame_b, float* d_record, int32_t w, int32_t h,
+                         void* stream);
+int bdpt_variance_buffers(int32_t device, const float* d_record, int32_t batches, int32_t w, int32_t h, float* d_var,
+                          void* stream);
+int bdpt_denoise_variance_buffers(int32_t device, const float* d_color, const float* d_var, const float* d_features, int32_t w,
+                                  int32_t h, const bdpt_denoise_variance_params* p, float* d_out, float* d_var_out,
+                                  void* stream);
 
 /* Host-side COLLADA loader: the reference CLI's scene path (ColladaParser::load,
  * collada.cpp:129-941, + Application::load, application.cpp:228-304). width/height > 0 apply
