@@ -93,6 +93,19 @@ class DenoiseVarianceParams(C.Structure):
                 ("sigma_depth", C.c_float), ("reserved", C.c_int32 * 4)]
 
 
+class AdaptiveParams(C.Structure):
+    """bdpt_adaptive_params: adaptive sampling under BDPT. adaptive_params() fills the
+    library's defaults; max_rounds 0 = spp / samples_per_round."""
+    _fields_ = [("samples_per_round", C.c_int32), ("min_rounds", C.c_int32), ("max_rounds", C.c_int32),
+                ("tolerance", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class AdaptiveInfo(C.Structure):
+    """bdpt_adaptive_info: rounds run, blocks still active at the end, pixel-samples rendered."""
+    _fields_ = [("rounds", C.c_int32), ("active_blocks", C.c_int32), ("samples", C.c_int64),
+                ("reserved", C.c_int32 * 4)]
+
+
 class Tile(C.Structure):
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
 
@@ -377,6 +390,25 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.bdpt_variance_buffers.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.bdpt_denoise_variance_buffers.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                                   C.POINTER(DenoiseVarianceParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bdpt_adaptive_default_params.argtypes = [C.c_void_p, C.POINTER(AdaptiveParams)]
+    lib.bdpt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveInfo)]
+    lib.bdpt_adaptive_resolve.argtypes = [C.c_void_p]
+    lib.bdpt_read_adaptive.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]
+    lib.bdpt_adaptive_device_ptrs.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_void_p)]
+    lib.bdpt_read_adaptive_rounds.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    lib.bdpt_read_adaptive_active.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    lib.bdpt_read_adaptive_records.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.bdpt_adaptive_moments_buffers.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                  C.c_int32, C.c_int64, C.c_void_p]
+    lib.bdpt_adaptive_decide_buffers.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_float,
+                                                 C.c_int32, C.c_void_p]
+    lib.bdpt_adaptive_compact_buffers.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
+    lib.bdpt_adaptive_resolve_buffers.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                  C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -492,6 +524,69 @@ def denoise_variance_buffers(color_ptr: int, var_ptr: int, features_ptr: int, wi
     _check(lib.bdpt_denoise_variance_buffers(device, C.c_void_p(color_ptr), C.c_void_p(var_ptr),
                                              C.c_void_p(features_ptr), width, height, C.byref(p), C.c_void_p(out_ptr),
                                              C.c_void_p(var_out_ptr or None), C.c_void_p(stream)), lib)
+
+
+def adaptive_params(samples_per_round: Optional[int] = None, min_rounds: Optional[int] = None,
+                    max_rounds: Optional[int] = None, tolerance: Optional[float] = None, ctx=None) -> AdaptiveParams:
+    """The library's default settings of the adaptive sampler (bdpt_adaptive_default_params) with the
+    given ones replaced. max_rounds None = 0 = spp / samples_per_round of the context that renders."""
+    lib = load_library()
+    p = AdaptiveParams()
+    _check(lib.bdpt_adaptive_default_params(ctx, C.byref(p)), lib)
+    if samples_per_round is not None:
+        p.samples_per_round = samples_per_round
+        if max_rounds is None:
+            p.max_rounds = 0
+    if min_rounds is not None:
+        p.min_rounds = min_rounds
+    if max_rounds is not None:
+        p.max_rounds = max_rounds
+    if tolerance is not None:
+        p.tolerance = tolerance
+    return p
+
+
+def adaptive_moments_buffers(eye_ptr: int, light_ptr: int, eye_record_ptr: int, light_record_ptr: int, width: int,
+                             height: int, round_samples: int, device: int = 0, stream: int = 0) -> None:
+    """bdpt_adaptive_moments_buffers: one round of `round_samples` pixel-samples into the eye and the
+    light record (W*H*4 floats each) from the raw eye and light frames (W*H*3). Async on `stream`."""
+    lib = load_library()
+    _check(lib.bdpt_adaptive_moments_buffers(device, C.c_void_p(eye_ptr), C.c_void_p(light_ptr), C.c_void_p(eye_record_ptr),
+                                             C.c_void_p(light_record_ptr), width, height, round_samples,
+                                             C.c_void_p(stream)), lib)
+
+
+def adaptive_decide_buffers(eye_record_ptr: int, light_record_ptr: int, rounds_ptr: int, active_ptr: int, width: int,
+                            height: int, spp: int, samples_per_round: int, rounds: int, samples: int, tolerance: float,
+                            decide: bool = True, device: int = 0, stream: int = 0) -> None:
+    """bdpt_adaptive_decide_buffers: K_b += 1 for the active blocks (one int32 per 8x8 block each) and,
+    with `decide`, the stopping rule after `rounds` rounds and `samples` pixel-samples. Async."""
+    lib = load_library()
+    _check(lib.bdpt_adaptive_decide_buffers(device, C.c_void_p(eye_record_ptr), C.c_void_p(light_record_ptr),
+                                            C.c_void_p(rounds_ptr), C.c_void_p(active_ptr), width, height, spp,
+                                            samples_per_round, rounds, samples, tolerance, 1 if decide else 0,
+                                            C.c_void_p(stream)), lib)
+
+
+def adaptive_compact_buffers(active_ptr: int, width: int, height: int, list_ptr: int, counts_ptr: int,
+                             device: int = 0, stream: int = 0) -> None:
+    """bdpt_adaptive_compact_buffers: the active blocks as {x, y, w, h} int32 in block order into the
+    list (room for every block) and {active blocks, their pixels} into the two counts. Async."""
+    lib = load_library()
+    _check(lib.bdpt_adaptive_compact_buffers(device, C.c_void_p(active_ptr), width, height, C.c_void_p(list_ptr),
+                                             C.c_void_p(counts_ptr), C.c_void_p(stream)), lib)
+
+
+def adaptive_resolve_buffers(eye_record_ptr: int, light_record_ptr: int, rounds_ptr: int, width: int, height: int, spp: int,
+                             samples_per_round: int, rounds: int, samples: int, color_ptr: int, var_ptr: int,
+                             counts_ptr: int, device: int = 0, stream: int = 0) -> None:
+    """bdpt_adaptive_resolve_buffers: colour (W*H*3), variance (W*H) and sample counts (W*H int32) of
+    the two records and the per-block round counts. Async."""
+    lib = load_library()
+    _check(lib.bdpt_adaptive_resolve_buffers(device, C.c_void_p(eye_record_ptr), C.c_void_p(light_record_ptr),
+                                             C.c_void_p(rounds_ptr), width, height, spp, samples_per_round, rounds,
+                                             samples, C.c_void_p(color_ptr), C.c_void_p(var_ptr), C.c_void_p(counts_ptr),
+                                             C.c_void_p(stream)), lib)
 
 
 def denoise_variance_tensor(color, var, features, out=None, var_out=None, **params):
@@ -709,6 +804,60 @@ class BidirectionalPathTracer:
         p = denoise_variance_params(**params)
         _check(self.lib.bdpt_denoise_variance(self.ctx, C.byref(p)), self.lib)
         return self.read_denoised()
+
+    # --- adaptive sampling -------------------------------------------------------
+    def _nblocks(self):
+        return (self.height + 7) // 8, (self.width + 7) // 8
+
+    def render_adaptive(self, **params) -> dict:
+        """Renders the cleared frame in rounds over the 8x8 blocks that have not yet met the tolerance
+        (params: samples_per_round, min_rounds, max_rounds, tolerance; adaptive_params). Synchronous.
+        Returns {"rounds", "samples", "active_blocks"}."""
+        p = adaptive_params(ctx=self.ctx, **params)
+        info = AdaptiveInfo()
+        _check(self.lib.bdpt_render_adaptive(self.ctx, C.byref(p), C.byref(info)), self.lib)
+        return {"rounds": int(info.rounds), "samples": int(info.samples), "active_blocks": int(info.active_blocks)}
+
+    def adaptive_resolve(self) -> None:
+        """Computes the colour, variance and sample-count frames of the adaptive render. Async."""
+        _check(self.lib.bdpt_adaptive_resolve(self.ctx), self.lib)
+
+    def read_adaptive(self) -> dict:
+        """{"color" (H, W, 3) float32, "variance" (H, W) float32, "counts" (H, W) int32} of the last
+        adaptive_resolve()."""
+        c = np.empty((self.height, self.width, 3), dtype=np.float32)
+        v = np.empty((self.height, self.width), dtype=np.float32)
+        n = np.empty((self.height, self.width), dtype=np.int32)
+        _check(self.lib.bdpt_read_adaptive(self.ctx, c.ctypes.data_as(C.POINTER(C.c_float)),
+                                           v.ctypes.data_as(C.POINTER(C.c_float)),
+                                           n.ctypes.data_as(C.POINTER(C.c_int32))), self.lib)
+        return {"color": c, "variance": v, "counts": n}
+
+    def read_adaptive_rounds(self) -> np.ndarray:
+        """K_b, the rounds each 8x8 block was active: (nby, nbx) int32."""
+        out = np.empty(self._nblocks(), dtype=np.int32)
+        _check(self.lib.bdpt_read_adaptive_rounds(self.ctx, out.ctypes.data_as(C.POINTER(C.c_int32))), self.lib)
+        return out
+
+    def read_adaptive_active(self) -> np.ndarray:
+        """The blocks' active flags after the last round: (nby, nbx) int32."""
+        out = np.empty(self._nblocks(), dtype=np.int32)
+        _check(self.lib.bdpt_read_adaptive_active(self.ctx, out.ctypes.data_as(C.POINTER(C.c_int32))), self.lib)
+        return out
+
+    def read_adaptive_records(self):
+        """(eye record, light record) as stored: (H, W, 4) float32 {prev.rgb, Q} each."""
+        e = np.empty((self.height, self.width, 4), dtype=np.float32)
+        l = np.empty((self.height, self.width, 4), dtype=np.float32)
+        _check(self.lib.bdpt_read_adaptive_records(self.ctx, e.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   l.ctypes.data_as(C.POINTER(C.c_float))), self.lib)
+        return e, l
+
+    def adaptive_device_ptrs(self) -> dict:
+        """Device pointers of the resolved frames: {"color", "variance", "counts"}."""
+        c, v, n = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(self.lib.bdpt_adaptive_device_ptrs(self.ctx, C.byref(c), C.byref(v), C.byref(n)), self.lib)
+        return {"color": c.value, "variance": v.value, "counts": n.value}
 
     def trace_rays(self, rays: np.ndarray, any_hit: bool = False):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)

@@ -90,7 +90,29 @@ struct Ctx {
   float* d_var_scratch = nullptr;
   int var_batches = 0, var_batch_spp = 0;
   bool var_unbatched = false, in_batches = false, variance_valid = false;
+  // Adaptive sampling (bdpt_adaptive.hip), all allocated by the first adaptive render:
+  // the eye and the light records (2 x W*H float4), per 8x8 block the rounds it was active and its
+  // active flag (2 x nblocks int), the compacted block list, its two counts {blocks, pixels} on the
+  // device and in pinned memory with the event of the per-round wait, and the resolved frames
+  // (colour W*H*3, variance W*H, counts W*H int32; allocated by the first resolve). frame_dirty: the
+  // frame holds samples since the last bdpt_clear; adapt_valid: they are an adaptive render's, of
+  // adapt_rounds rounds of adapt_m samples and adapt_n pixel-samples in all.
+  float* d_adapt_rec = nullptr;
+  int* d_adapt_rounds = nullptr;
+  int4* d_adapt_list = nullptr;
+  int* d_adapt_counts = nullptr;
+  int* h_adapt_counts = nullptr;
+  hipEvent_t adapt_ev = nullptr;
+  float* d_adapt_out = nullptr;
+  int adapt_rounds = 0, adapt_m = 0, adapt_active = 0;
+  long long adapt_n = 0;
+  bool frame_dirty = false, adapt_valid = false, adapt_resolved = false;
 };
+
+// The launch half of bdpt_render (bdpt_hip.hip): samples [spp_begin, spp_begin + spp_count) of the
+// nblocks 8x8 pixel blocks {x, y, w, h} at d_blocks (device memory), or of the whole frame when
+// d_blocks is null. The caller holds c->mu and has set the device.
+int render_blocks(Ctx* c, const int4* d_blocks, int nblocks, int spp_begin, int spp_count);
 
 #define HIPCHK(x)                                                                   \
   do {                                                                              \

@@ -211,9 +211,12 @@ void free_ctx(Ctx* c) {
   if (!c) return;
   void* bufs[] = {c->d_nodes2, c->d_nodes4, c->d_geom, c->d_shade, c->d_mats, c->d_lights, c->d_prim_ref, c->d_env, c->d_count, c->d_work8, c->d_leaves,
                   c->d_eye, c->d_light, c->d_sample, c->d_stats, c->d_features, c->d_denoised, c->d_dn_scratch,
-                  c->d_feat_blocks, c->d_moments, c->d_variance, c->d_var_scratch};
+                  c->d_feat_blocks, c->d_moments, c->d_variance, c->d_var_scratch, c->d_adapt_rec, c->d_adapt_rounds,
+                  c->d_adapt_list, c->d_adapt_counts, c->d_adapt_out};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  if (c->h_adapt_counts) (void)hipHostFree(c->h_adapt_counts);
+  if (c->adapt_ev) (void)hipEventDestroy(c->adapt_ev);
   for (Ctx::BlockSlot& b : c->blk) {
     if (b.d) (void)hipFree(b.d);
     if (b.h) (void)hipHostFree(b.h);
@@ -391,6 +394,13 @@ int bdpt_clear(void* ctx) {
   if (c->d_moments) HIPCHK(hipMemsetAsync(c->d_moments, 0, c->npix * 4 * sizeof(float), c->stream));
   c->var_batches = c->var_batch_spp = 0;
   c->var_unbatched = c->variance_valid = false;
+  // the adaptive records, round counts and flags (bdpt_adaptive.hip) start over too
+  if (c->d_adapt_rec) HIPCHK(hipMemsetAsync(c->d_adapt_rec, 0, 2 * c->npix * 4 * sizeof(float), c->stream));
+  if (c->d_adapt_rounds)
+    HIPCHK(hipMemsetAsync(c->d_adapt_rounds, 0, 2 * (size_t)((c->prm.width + 7) / 8) * ((c->prm.height + 7) / 8) * sizeof(int), c->stream));
+  c->adapt_rounds = c->adapt_m = c->adapt_active = 0;
+  c->adapt_n = 0;
+  c->frame_dirty = c->adapt_valid = c->adapt_resolved = false;
   return BDPT_OK;
 }
 
@@ -402,24 +412,12 @@ int bdpt_render(void* ctx, const bdpt_tile* tiles, int32_t ntiles, int32_t spp_b
   if (spp_count == 0) return BDPT_OK;
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   if (!c->in_batches) c->var_unbatched = true;   // samples outside bdpt_render_batches: no variance of this frame
+  c->frame_dirty = true;                         // bdpt_render_adaptive starts from a cleared frame only,
+  c->adapt_valid = false;                        // and its per-block estimate no longer describes this one
   HIPCHK(hipSetDevice(c->device));
   const int W = c->prm.width, H = c->prm.height;
-  KParams kp;
-  kp.S = view_of(c, 0);   // launch_lm sets the LDS mode's view
-  kp.sp.W = W; kp.sp.H = H; kp.sp.spp = c->prm.spp; kp.sp.max_depth = c->prm.max_depth; kp.sp.seed = c->prm.seed;
-  kp.sp.rr = c->prm.russian_roulette != 0;
-  kp.sp.focal = lens_focal(c->prm.focal_distance);   // read by the lens kernels only (§9b)
-  kp.eye = c->d_eye;
-  kp.light = c->d_light;
-  kp.stats = c->d_stats;
-  kp.prof = c->d_stats + 16;
-  kp.n_geom4 = (int)(c->hs.geom.size() / 4);
-  kp.nmat = (int)c->hs.mats.size();
-  kp.item_lo = 0;
-  kp.lstack_on = 0;
-  kp.blocks = nullptr;
-  kp.nbx = (W + 7) / 8;
-  kp.nblocks = kp.nbx * ((H + 7) / 8);
+  const int4* d_blocks = nullptr;
+  int nblocks = 0;
   Ctx::BlockSlot* slot = nullptr;
   if (tiles && ntiles > 0) {
     // Tiles (raytrace_tile clips them to the frame, raytraced_renderer.cpp:600-604) -> 8x8 blocks.
@@ -446,8 +444,8 @@ int bdpt_render(void* ctx, const bdpt_tile* tiles, int32_t ntiles, int32_t spp_b
     }
     memcpy(slot->h, blk.data(), blk.size() * sizeof(int4));
     HIPCHK(hipMemcpyAsync(slot->d, slot->h, blk.size() * sizeof(int4), hipMemcpyHostToDevice, c->stream));
-    kp.blocks = slot->d;
-    kp.nblocks = (int)blk.size();
+    d_blocks = slot->d;
+    nblocks = (int)blk.size();
   }
   // the slot is free again once everything enqueued below has run (on every return path)
   struct SlotRelease {
@@ -458,6 +456,34 @@ int bdpt_render(void* ctx, const bdpt_tile* tiles, int32_t ntiles, int32_t spp_b
       else if (s) (void)hipStreamSynchronize(st);
     }
   } slot_release{slot, c->stream};
+  return render_blocks(c, d_blocks, nblocks, spp_begin, spp_count);
+}
+
+}  // extern "C"
+
+// The second half of bdpt_render: the launch over a device list of 8x8 pixel blocks (null: the frame).
+int bdpt::render_blocks(Ctx* c, const int4* d_blocks, int nblocks, int spp_begin, int spp_count) {
+  const int W = c->prm.width, H = c->prm.height;
+  KParams kp;
+  kp.S = view_of(c, 0);   // launch_lm sets the LDS mode's view
+  kp.sp.W = W; kp.sp.H = H; kp.sp.spp = c->prm.spp; kp.sp.max_depth = c->prm.max_depth; kp.sp.seed = c->prm.seed;
+  kp.sp.rr = c->prm.russian_roulette != 0;
+  kp.sp.focal = lens_focal(c->prm.focal_distance);   // read by the lens kernels only (§9b)
+  kp.eye = c->d_eye;
+  kp.light = c->d_light;
+  kp.stats = c->d_stats;
+  kp.prof = c->d_stats + 16;
+  kp.n_geom4 = (int)(c->hs.geom.size() / 4);
+  kp.nmat = (int)c->hs.mats.size();
+  kp.item_lo = 0;
+  kp.lstack_on = 0;
+  kp.blocks = nullptr;
+  kp.nbx = (W + 7) / 8;
+  kp.nblocks = kp.nbx * ((H + 7) / 8);
+  if (d_blocks) {
+    kp.blocks = d_blocks;
+    kp.nblocks = nblocks;
+  }
   if (c->pt) {   // the PathTracer renders whole pixels (adaptive sampling decides per pixel)
     if (spp_begin != 0 || spp_count != c->prm.spp) {
       g_err = "the PathTracer renders whole pixels: spp_begin must be 0 and spp_count the ctx's spp";
@@ -526,6 +552,8 @@ int bdpt_render(void* ctx, const bdpt_tile* tiles, int32_t ntiles, int32_t spp_b
   c->timed = true;
   return BDPT_OK;
 }
+
+extern "C" {
 
 int bdpt_sync(void* ctx) {
   Ctx* c = (Ctx*)ctx;

@@ -5,7 +5,7 @@
 //              [-l n] [-e envmap.exr] [--rr] [--infinite-lights] [-g gpus] [-S seed] [--dump-scene scene.json]
 //              [--pt [-a batch tol] [-H] [-b lens] [-d focal]] [--thin-lens [-b lens] [-d focal]]
 //              [--denoise] [--features] [--denoise-levels n] [--denoise-sigma c n d] [--feature-spp n]
-//              [--denoise-batches k] [--denoise-sigma-variance v] scene.dae
+//              [--denoise-batches k] [--denoise-sigma-variance v] [--adaptive [-a batch tol]] scene.dae
 //
 // Same flags and defaults as the reference (-s 1, -m 1, 800x600 when -r is absent; -t / -l are
 // accepted and do not apply to the GPU path; -p renders one cell). -g N splits the sample range
@@ -28,6 +28,12 @@
 // then the variance-guided filter (--denoise-sigma-variance overrides its sigma_variance,
 // --denoise-levels its levels, --denoise-sigma's N and D its other two sigmas), and --features also
 // writes "<name>_stderr.png": the pixel's standard error sqrt(v) as a grey through the tonemap.
+// --adaptive (BDPT, one GPU, whole frame) renders in rounds of -a's BATCH samples and stops every 8x8
+// pixel block once 1.96 x its standard error is within -a's TOL of its mean (bdpt_render_adaptive,
+// DESIGN.md §13); -s is the cap and BATCH must divide it. The PNG is the resolved colour, "_rate.png"
+// the per-pixel sample count over -s; --denoise is the variance-guided filter on the resolved colour
+// and variance, --features also writes "<name>_stderr.png"; the report's ray counters are skipped.
+// Without --adaptive, -a under BDPT stays ignored.
 // Output: the tonemapped PNG and the "_rate.png" sampling-rate image, as render_to_file writes
 // them (raytraced_renderer.cpp:330-347, 690-761). The "Rendering... 100%! (Xs)" time covers the
 // production kernel's render, the frame reduce and the frame read-back; bdpt_create (BVH build + upload) runs before
@@ -82,6 +88,9 @@ void usage(const char* b) {
          "                   their per-pixel variance: --denoise becomes the variance-guided filter, --features\n"
          "                   also writes <name>_stderr.png (the standard error through the tonemap)\n");
   printf("  --denoise-sigma-variance <V>  Variance-guided filter: sigma_variance (default: the library's)\n");
+  printf("  --adaptive       BDPT (-g 1, no -p, no --denoise-batches): render in rounds of -a's BATCH samples (it must\n"
+         "                   divide -s, the cap) and stop each 8x8 block at -a's TOL; writes the resolved colour and\n"
+         "                   counts / spp as <name>_rate.png\n");
   printf("  --dump-scene <FILE>  Write the loaded scene as JSON\n");
   printf("  --no-stats       Skip the ray / intersection-test counters of the end-of-render report\n");
   printf("  --tonemap <in.f64> <W> <H> <out.png>  Output stage only: raw float64 RGB (row 0 =\n"
@@ -116,6 +125,7 @@ int main(int argc, char** argv) {
   bool rr = false, pt = false, hemi = false, stats = true, inf_lights = false, thin_lens = false;
   bool denoise = false, features = false;
   int dn_levels = -1, feature_spp = 0, dn_batches = 0;
+  bool adaptive = false;
   float dn_sigma_var = 0;
   float dn_sigma[3] = {0, 0, 0};
   int nal = 1, batch = 32;
@@ -162,6 +172,7 @@ int main(int argc, char** argv) {
     else if (a == "--denoise-sigma") { need(3); for (int k = 0; k < 3; k++) dn_sigma[k] = (float)atof(argv[i + 1 + k]); i += 3; }
     else if (a == "--feature-spp") { need(1); feature_spp = atoi(argv[++i]); }
     else if (a == "--denoise-batches") { need(1); dn_batches = atoi(argv[++i]); }
+    else if (a == "--adaptive") adaptive = true;
     else if (a == "--denoise-sigma-variance") { need(1); dn_sigma_var = (float)atof(argv[++i]); }
     else if (a == "--tonemap") {
       need(4);
@@ -185,6 +196,15 @@ int main(int argc, char** argv) {
   if (dn_batches != 0 && (dn_batches < 2 || spp % dn_batches != 0 || pt || gpus != 1 || cx >= 0)) {
     fprintf(stderr, "[PathTracer] --denoise-batches K: K >= 2 must divide -s, under BDPT, with -g 1 and without -p\n");
     return 1;
+  }
+  if (adaptive) {   // BDPT in rounds of -a's BATCH, stopped per 8x8 block at -a's TOL
+    const char* why = pt ? "--adaptive is BDPT's; the PathTracer (--pt) stops single pixels with -a alone"
+                      : gpus != 1 ? "--adaptive renders on one GPU (-g 1)"
+                      : cx >= 0 ? "--adaptive renders the whole frame (no -p)"
+                      : dn_batches != 0 ? "--adaptive keeps its own records: not together with --denoise-batches"
+                      : batch < 1 || spp % batch != 0 ? "--adaptive: -a's BATCH must be >= 1 and divide -s"
+                      : nullptr;
+    if (why) { fprintf(stderr, "[PathTracer] %s\n", why); return 1; }
   }
   fprintf(stderr, "[PathTracer] Input scene file: %s\n", scene.c_str());
   bdpt_dae* dae = nullptr;
@@ -227,6 +247,8 @@ int main(int argc, char** argv) {
   std::vector<void*> ctxs(gpus, nullptr);
   std::vector<std::vector<bdpt_tile>> mine(gpus, tiles);
   std::vector<int> s0(gpus), s1(gpus);
+  bdpt_adaptive_info ainfo;
+  memset(&ainfo, 0, sizeof ainfo);
   auto params = [&](int g, bool count) {
     bdpt_params p;
     memset(&p, 0, sizeof p);
@@ -267,7 +289,16 @@ int main(int argc, char** argv) {
           bdpt_params p = params(g, false);
           rc = bdpt_create(&desc, &p, &ctxs[g]);
         } else if (phase == 1) {
-          if (s1[g] > s0[g] && dn_batches > 0)
+          if (adaptive) {
+            bdpt_adaptive_params ap;
+            bdpt_adaptive_default_params(ctxs[g], &ap);
+            ap.samples_per_round = batch;
+            ap.max_rounds = spp / batch;
+            ap.min_rounds = std::min(ap.min_rounds, ap.max_rounds);
+            ap.tolerance = tol;
+            rc = bdpt_render_adaptive(ctxs[g], &ap, &ainfo);
+            if (rc == BDPT_OK) rc = bdpt_adaptive_resolve(ctxs[g]);
+          } else if (s1[g] > s0[g] && dn_batches > 0)
             rc = bdpt_render_batches(ctxs[g], s0[g], s1[g] - s0[g], dn_batches);
           else if (s1[g] > s0[g])
             rc = bdpt_render(ctxs[g], mine[g].empty() ? nullptr : mine[g].data(), (int32_t)mine[g].size(), s0[g], s1[g] - s0[g]);
@@ -325,8 +356,16 @@ int main(int argc, char** argv) {
   auto t0 = std::chrono::steady_clock::now();
   if (!run(1)) { cleanup(); return 1; }
   // every device's partial frame summed into context 0's over xGMI, then one read-back
-  if ((red && bdpt_reduce_frames(red, 0) != BDPT_OK) || bdpt_read_frame(ctxs[0], BDPT_FRAME_SAMPLE, img.data()) != BDPT_OK ||
-      bdpt_read_sample_counts(ctxs[0], count.data()) != BDPT_OK) {
+  std::vector<float> feat, den, var;
+  if (adaptive) {   // the resolved colour, its variance and the per-pixel sample counts
+    var.resize((size_t)w * h);
+    if (bdpt_read_adaptive(ctxs[0], img.data(), var.data(), count.data()) != BDPT_OK) {
+      fail("reading the adaptive frame");
+      cleanup();
+      return 1;
+    }
+  } else if ((red && bdpt_reduce_frames(red, 0) != BDPT_OK) || bdpt_read_frame(ctxs[0], BDPT_FRAME_SAMPLE, img.data()) != BDPT_OK ||
+             bdpt_read_sample_counts(ctxs[0], count.data()) != BDPT_OK) {
     fail("reducing the frames");
     cleanup();
     return 1;
@@ -334,7 +373,9 @@ int main(int argc, char** argv) {
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   // --denoise / --features: the feature pass and the filter on context 0, which holds the whole
   // frame (after the reduce with -g N); outside the render's timer
-  std::vector<float> feat, den, var;
+  if (adaptive)
+    fprintf(stderr, "[PathTracer] adaptive: %d rounds of %d samples, %.2f samples per pixel on average, %d blocks at the cap\n",
+            ainfo.rounds, batch, (double)ainfo.samples / ((double)w * h), ainfo.active_blocks);
   if (dn_batches > 0 && (denoise || features)) {
     var.resize((size_t)w * h);
     if (bdpt_variance(ctxs[0]) != BDPT_OK || bdpt_read_variance(ctxs[0], var.data()) != BDPT_OK) {
@@ -351,7 +392,27 @@ int main(int argc, char** argv) {
       cleanup();
       return 1;
     }
-    if (denoise && dn_batches > 0) {
+    if (denoise && adaptive) {
+      // the resolved colour and variance through the variance-guided filter, in place on the
+      // context's device frames (img holds the unfiltered colour already)
+      bdpt_denoise_variance_params vp;
+      bdpt_denoise_variance_default_params(&vp);
+      if (dn_levels >= 0) vp.levels = dn_levels;
+      if (dn_sigma_var != 0) vp.sigma_variance = dn_sigma_var;
+      if (dn_sigma[0] != 0 || dn_sigma[1] != 0 || dn_sigma[2] != 0) { vp.sigma_normal = dn_sigma[1]; vp.sigma_depth = dn_sigma[2]; }
+      den.resize((size_t)w * h * 3);
+      void *dc = nullptr, *dv = nullptr, *df = nullptr;
+      const int dev = devices.empty() ? 0 : devices[0];
+      if (bdpt_adaptive_device_ptrs(ctxs[0], &dc, &dv, nullptr) != BDPT_OK || bdpt_features_device_ptr(ctxs[0], &df) != BDPT_OK ||
+          bdpt_sync(ctxs[0]) != BDPT_OK ||
+          bdpt_denoise_variance_buffers(dev, (const float*)dc, (const float*)dv, (const float*)df, w, h, &vp, (float*)dc, nullptr,
+                                        nullptr) != BDPT_OK ||
+          bdpt_read_adaptive(ctxs[0], den.data(), nullptr, nullptr) != BDPT_OK) {
+        fail("denoising");
+        cleanup();
+        return 1;
+      }
+    } else if (denoise && dn_batches > 0) {
       bdpt_denoise_variance_params vp;
       bdpt_denoise_variance_default_params(&vp);
       if (dn_levels >= 0) vp.levels = dn_levels;
@@ -381,8 +442,9 @@ int main(int argc, char** argv) {
             std::chrono::duration<double>(std::chrono::steady_clock::now() - tf).count());
   }
   release();
+  if (adaptive) stats = false;   // the instrumented kernel would count a uniform render's rays
   if (stats && !run(2)) { cleanup(); return 1; }
-  const double samples = (double)(tiles.empty() ? (long long)w * h : cdx * cdy) * spp;
+  const double samples = adaptive ? (double)ainfo.samples : (double)(tiles.empty() ? (long long)w * h : cdx * cdy) * spp;
   // the reference's end-of-render report (raytraced_renderer.cpp:679-682), on stdout: time, rays
   // traced (closest-hit walk rays + connection rays), Mrays/s, primitive tests per ray
   fprintf(stdout, "[PathTracer] Rendering... 100%%! (%.4fs)\n", secs);
@@ -416,7 +478,7 @@ int main(int argc, char** argv) {
   }
   fprintf(stderr, "Done!\n");
   std::vector<float> rate((size_t)w * h, 0.0f);
-  if (pt) {   // sampleCountBuffer[k] * 1.0f / ns_aa (save_sampling_rate_image, raytraced_renderer.cpp:737)
+  if (pt || adaptive) {   // sampleCountBuffer[k] * 1.0f / ns_aa (save_sampling_rate_image, raytraced_renderer.cpp:737)
     for (size_t k = 0; k < rate.size(); k++) rate[k] = count[k] * 1.0f / spp;   // summed by the reduce
   } else if (tiles.empty()) {
     std::fill(rate.begin(), rate.end(), 1.0f);   // every pixel got ns_aa samples (bidirection.cpp:539)

@@ -45,6 +45,9 @@
  * Variance-guided denoise (new symbols only as well): a frame rendered in equal sample
  * batches keeps per-pixel moments (bdpt_render_batches), which give its per-pixel variance
  * (bdpt_variance) and guide the filter's colour weight (bdpt_denoise_variance, *_buffers).
+ * Adaptive sampling under BDPT (new symbols only as well): the frame is rendered in
+ * rounds and every 8x8 pixel block stops once its variance is within a tolerance of its mean
+ * (bdpt_render_adaptive, bdpt_adaptive_resolve, bdpt_read_adaptive, bdpt_adaptive_*_buffers).
  * And the reference's second integrator: the unidirectional PathTracer
  * (pathtracer.cpp:47-340 — NEE, adaptive sampling, thin lens, roulette at -m 0, the environment
  * light, MicrofacetBSDF), selected by bdpt_params.integrator = BDPT_INTEGRATOR_PT (ABI v3).
@@ -426,6 +429,79 @@ int bdpt_variance_buffers(int32_t device, const float* d_record, int32_t batches
 int bdpt_denoise_variance_buffers(int32_t device, const float* d_color, const float* d_var, const float* d_features, int32_t w,
                                   int32_t h, const bdpt_denoise_variance_params* p, float* d_out, float* d_var_out,
                                   void* stream);
+
+/* Adaptive sampling under BDPT (new symbols, the ABI version stays 10). The frame is
+ * rendered in rounds of m = samples_per_round samples over the 8x8 pixel blocks of bdpt_render's
+ * whole-frame grid (nbx = (W+7)/8, edge blocks clipped). Round r renders samples [r m, (r+1) m) of the
+ * pixels of the blocks still active; a block that has stopped never restarts, so a pixel of a block
+ * that was active for K_b rounds holds samples [0, K_b m). With S the ctx's spp (every sample weighs
+ * 1/S in the raw frames E and L), R rounds, M_r the pixel-samples of round r and N their sum:
+ *   colour    c = fl(fl(a_b E) + fl(g L)),  a_b = S / (K_b m),  g = S W H / N
+ *   records   eye   {E.rgb, Q_E}: b = E - prev, Q_E += (b.x^2 + b.y^2) + b.z^2
+ *             light {L.rgb, Q_L}: b = L - prev, Q_L += ((b.x^2 + b.y^2) + b.z^2) fl(1 / M_r)
+ *   variance  v = a_b^2 K_b/(K_b-1) max(0, Q_E - |E|^2/K_b) + g^2 N/(R-1) max(0, Q_L - |L|^2/N),
+ * the trace of the covariance of c in bdpt_variance's units, without the eye-light covariance of a
+ * pixel (only the pixel's own K_b m of the N light subpaths correlate with its eye samples).
+ * After each round R >= min_rounds a block of n in-frame pixels stops iff
+ *   3.8416 Sv (3 n) <= (tol Sc)^2,   Sv = sum v,   Sc = sum (c.x + c.y) + c.z,
+ * i.e. 1.96 x the RMS per-channel standard error <= tol x the mean channel value; both sums are
+ * xor-butterflies over the block's 64 lanes (lane = x + 8 y, strides 32 .. 1, out-of-frame lanes +0).
+ * The render ends when no block is active or after max_rounds rounds. min_rounds == max_rounds
+ * == S / m is a uniform render: a_b = g = 1 and c is BDPT_FRAME_SAMPLE bit for bit. */
+typedef struct bdpt_adaptive_params {
+  int32_t samples_per_round; /* m >= 1; default 32                                               */
+  int32_t min_rounds;        /* rounds before the first decision, >= 2; default 4                 */
+  int32_t max_rounds;        /* >= min_rounds, max_rounds x m <= spp; 0 = spp / m (the default)    */
+  float tolerance;           /* tol >= 0, finite; default 0.05                                    */
+  int32_t reserved[4];       /* 0                                                                 */
+} bdpt_adaptive_params;
+typedef struct bdpt_adaptive_info {
+  int32_t rounds;            /* R: rounds run                                                     */
+  int32_t active_blocks;     /* blocks still active at the end (they ran into max_rounds)          */
+  int64_t samples;           /* N: pixel-samples (= light subpaths) rendered                      */
+  int32_t reserved[4];
+} bdpt_adaptive_info;
+/* The defaults; ctx may be NULL (max_rounds stays 0 = spp / samples_per_round). No device is touched. */
+int bdpt_adaptive_default_params(void* ctx, bdpt_adaptive_params* p);
+/* Renders the whole frame adaptively (params NULL: the defaults) and returns when it is done (one host
+ * wait per round); `out` may be NULL. BDPT_E_UNSUPPORTED under the PathTracer. BDPT_E_INVALID for
+ * parameters outside the ranges above and for a frame that already holds samples (bdpt_render,
+ * bdpt_render_batches or an earlier adaptive render since bdpt_clear). Afterwards the raw frames hold
+ * unequal sample counts: read the image with bdpt_adaptive_resolve / bdpt_read_adaptive;
+ * bdpt_variance refuses the frame; a bdpt_render invalidates the adaptive state until bdpt_clear,
+ * which zeroes the records, the K_b, N and the flags. bdpt_read_sample_counts is unchanged. */
+int bdpt_render_adaptive(void* ctx, const bdpt_adaptive_params* params, bdpt_adaptive_info* out);
+/* Computes c, v and the per-pixel sample count K_b m from the records (frames allocated on first use).
+ * Async. BDPT_E_INVALID before an adaptive render. */
+int bdpt_adaptive_resolve(void* ctx);
+/* The resolved frames: rgb W*H*3 floats, var W*H floats, counts W*H int32, row 0 = bottom (sync); any
+ * pointer may be NULL. BDPT_E_INVALID before bdpt_adaptive_resolve. */
+int bdpt_read_adaptive(void* ctx, float* rgb, float* var, int32_t* counts);
+int bdpt_adaptive_device_ptrs(void* ctx, void** d_color, void** d_var, void** d_counts);
+/* Per block, in block-index order (nbx x nby int32): K_b, and the active flag (1 = the block ran into
+ * max_rounds) (sync). */
+int bdpt_read_adaptive_rounds(void* ctx, int32_t* per_block);
+int bdpt_read_adaptive_active(void* ctx, int32_t* per_block);
+/* The raw records, W*H*4 floats each (sync); either pointer may be NULL. */
+int bdpt_read_adaptive_records(void* ctx, float* eye_rec4, float* light_rec4);
+/* The four kernels on caller device memory of `device`, without a ctx, enqueued on `stream`; all
+ * async. The records (w*h*4 floats) and d_list4 are 16-byte aligned. d_rounds / d_active: one int32 per
+ * block. bdpt_adaptive_moments_buffers: one round into the two records, round_samples = M_r.
+ * bdpt_adaptive_decide_buffers: K_b += 1 for the active blocks and, when decide != 0, the stopping rule
+ * after `rounds` rounds with `samples` pixel-samples in all (rounds >= 2). bdpt_adaptive_compact_buffers:
+ * the active blocks as {x, y, w, h} in block order into d_list4 (room for every block) and
+ * d_counts2 = {active blocks, their pixels}. bdpt_adaptive_resolve_buffers: c (w*h*3), v (w*h) and
+ * K_b m (w*h int32). */
+int bdpt_adaptive_moments_buffers(int32_t device, const float* d_eye, const float* d_light, float* d_eye_record, float* d_light_record,
+                                  int32_t w, int32_t h, int64_t round_samples, void* stream);
+int bdpt_adaptive_decide_buffers(int32_t device, const float* d_eye_record, const float* d_light_record, int32_t* d_rounds,
+                                 int32_t* d_active, int32_t w, int32_t h, int32_t spp, int32_t samples_per_round, int32_t rounds,
+                                 int64_t samples, float tolerance, int32_t decide, void* stream);
+int bdpt_adaptive_compact_buffers(int32_t device, const int32_t* d_active, int32_t w, int32_t h, int32_t* d_list4, int32_t* d_counts2,
+                                  void* stream);
+int bdpt_adaptive_resolve_buffers(int32_t device, const float* d_eye_record, const float* d_light_record, const int32_t* d_rounds,
+                                  int32_t w, int32_t h, int32_t spp, int32_t samples_per_round, int32_t rounds, int64_t samples,
+                                  float* d_color, float* d_var, int32_t* d_counts, void* stream);
 
 /* Host-side COLLADA loader: the reference CLI's scene path (ColladaParser::load,
  * collada.cpp:129-941, + Application::load, application.cpp:228-304). width/height > 0 apply
