@@ -10,19 +10,18 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdint>
 #include <mutex>
 #include <string>
 
 #include "bdpt/bdpt.h"
 #include "bdpt_adaptive.h"
-#include "bdpt_ctx.h"
+#include "bdpt_launch.h"   // bdpt_ctx.h
+#include "bdpt_tile.h"
 
 using namespace bdpt;
 
 namespace {
 
-constexpr int kLinBlock = 256;
 constexpr int kWaveBlock = 256;      // k_adapt_decide: four waves = four pixel blocks
 constexpr int kCompactBlock = 1024;  // k_adapt_compact: one workgroup of 16 waves
 
@@ -125,7 +124,6 @@ __global__ __launch_bounds__(kLinBlock) void k_adapt_resolve(const float4* rec_e
   count[i] = K * m;
 }
 
-unsigned lin_grid(size_t npix) { return (unsigned)((npix + kLinBlock - 1) / kLinBlock); }
 int nblocks_of(int W, int H) { return ((W + kAdaptBlock - 1) / kAdaptBlock) * ((H + kAdaptBlock - 1) / kAdaptBlock); }
 unsigned wave_grid(int nblocks) { return (unsigned)((nblocks + kWaveBlock / 64 - 1) / (kWaveBlock / 64)); }
 
@@ -162,14 +160,6 @@ int check_params(const bdpt_adaptive_params* p, int spp, bdpt_adaptive_params* o
   return BDPT_OK;
 }
 
-int check_frame(int32_t device, int32_t w, int32_t h) {
-  if (w <= 0 || h <= 0) { g_err = "invalid frame size"; return BDPT_E_INVALID; }
-  if (device < 0) { g_err = "bad device ordinal"; return BDPT_E_INVALID; }
-  return BDPT_OK;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // The scalars of a decision or a resolve: what the callers of adapt_scal must hold.
 int check_totals(int32_t spp, int32_t m, int32_t rounds, int64_t samples) {
   if (spp < 1 || m < 1) { g_err = "spp and samples_per_round must be >= 1"; return BDPT_E_INVALID; }
@@ -181,14 +171,11 @@ int check_totals(int32_t spp, int32_t m, int32_t rounds, int64_t samples) {
 // The adaptive buffers of a context, allocated on the first adaptive render.
 int alloc_state(Ctx* c) {
   const int nb = nblocks_of(c->prm.width, c->prm.height);
-  auto need = [](auto** p, size_t bytes) { return *p != nullptr || hipMalloc((void**)p, bytes) == hipSuccess; };
-  const bool fresh = c->d_adapt_rec == nullptr;
-  if (!need(&c->d_adapt_rec, 2 * c->npix * sizeof(float4)) || !need(&c->d_adapt_rounds, 2 * (size_t)nb * sizeof(int)) ||
-      !need(&c->d_adapt_list, (size_t)nb * sizeof(int4)) || !need(&c->d_adapt_counts, 2 * sizeof(int))) {
-    g_err = "out of device memory";
-    return BDPT_E_NOMEM;
-  }
-  if (fresh) HIPCHK(hipMemsetAsync(c->d_adapt_rec, 0, 2 * c->npix * sizeof(float4), c->stream));
+  int rc;
+  if ((rc = ensure_alloc(&c->d_adapt_rec, 2 * c->npix * sizeof(float4), &c->stream)) ||
+      (rc = ensure_alloc(&c->d_adapt_rounds, 2 * (size_t)nb * sizeof(int))) ||
+      (rc = ensure_alloc(&c->d_adapt_list, (size_t)nb * sizeof(int4))) || (rc = ensure_alloc(&c->d_adapt_counts, 2 * sizeof(int))))
+    return rc;
   if (!c->h_adapt_counts) HIPCHK(hipHostMalloc((void**)&c->h_adapt_counts, 2 * sizeof(int)));
   if (!c->adapt_ev) HIPCHK(hipEventCreateWithFlags(&c->adapt_ev, hipEventDisableTiming));
   return BDPT_OK;
@@ -284,10 +271,8 @@ int bdpt_adaptive_resolve(void* ctx) {
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   if (!c->adapt_valid) { g_err = "bdpt_adaptive_resolve needs an adaptive render of this frame first (bdpt_render_adaptive)"; return BDPT_E_INVALID; }
   HIPCHK(hipSetDevice(c->device));
-  if (!c->d_adapt_out && hipMalloc((void**)&c->d_adapt_out, c->npix * 5 * sizeof(float)) != hipSuccess) {
-    g_err = "out of device memory";
-    return BDPT_E_NOMEM;
-  }
+  const int rc = ensure_alloc(&c->d_adapt_out, c->npix * 5 * sizeof(float));
+  if (rc) return rc;
   const int W = c->prm.width, H = c->prm.height;
   const float4* rec_e = (const float4*)c->d_adapt_rec;
   hipLaunchKernelGGL(k_adapt_resolve, dim3(lin_grid(c->npix)), dim3(kLinBlock), 0, c->stream, rec_e, rec_e + c->npix,
@@ -323,29 +308,18 @@ int bdpt_adaptive_device_ptrs(void* ctx, void** d_color, void** d_var, void** d_
   return BDPT_OK;
 }
 
-int bdpt_read_adaptive_rounds(void* ctx, int32_t* per_block) {
+// One half of Ctx::d_adapt_rounds: the blocks' round counts (half 0) or their active flags (half 1).
+static int read_per_block(void* ctx, int half, int32_t* per_block) {
   Ctx* c = (Ctx*)ctx;
   if (!c || !per_block) { g_err = "null argument"; return BDPT_E_INVALID; }
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   if (!c->adapt_valid) { g_err = "no adaptive render on this context (bdpt_render_adaptive)"; return BDPT_E_INVALID; }
-  HIPCHK(hipSetDevice(c->device));
   const size_t nb = (size_t)nblocks_of(c->prm.width, c->prm.height);
-  HIPCHK(hipMemcpyAsync(per_block, c->d_adapt_rounds, nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BDPT_OK;
+  return read_back(c, per_block, c->d_adapt_rounds + half * nb, nb * sizeof(int32_t));
 }
 
-int bdpt_read_adaptive_active(void* ctx, int32_t* per_block) {
-  Ctx* c = (Ctx*)ctx;
-  if (!c || !per_block) { g_err = "null argument"; return BDPT_E_INVALID; }
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  if (!c->adapt_valid) { g_err = "no adaptive render on this context (bdpt_render_adaptive)"; return BDPT_E_INVALID; }
-  HIPCHK(hipSetDevice(c->device));
-  const size_t nb = (size_t)nblocks_of(c->prm.width, c->prm.height);
-  HIPCHK(hipMemcpyAsync(per_block, c->d_adapt_rounds + nb, nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BDPT_OK;
-}
+int bdpt_read_adaptive_rounds(void* ctx, int32_t* per_block) { return read_per_block(ctx, 0, per_block); }
+int bdpt_read_adaptive_active(void* ctx, int32_t* per_block) { return read_per_block(ctx, 1, per_block); }
 
 int bdpt_read_adaptive_records(void* ctx, float* eye_rec4, float* light_rec4) {
   Ctx* c = (Ctx*)ctx;

@@ -16,12 +16,10 @@
 #include <cstring>
 #include <mutex>
 #include <string>
-#include <vector>
 
 #include "bdpt/bdpt.h"
 #include "bdpt_core.h"
-#include "bdpt_ctx.h"
-#include "bdpt_megakernel.h"
+#include "bdpt_launch.h"   // bdpt_ctx.h, bdpt_megakernel.h, bdpt_ldsplan.h
 #include "bdpt_scene.h"
 
 using namespace bdpt;
@@ -96,78 +94,38 @@ __global__ void k_combine(const float* a, const float* b, float* out, long long 
   if (i < n) out[i] = a[i] + b[i];
 }
 
-// LDS budget for the scene copy: 160 KB per CU shared by the blocks that the 4-waves/SIMD VGPR
-// budget admits (16 waves per CU), minus their wave queues.
-constexpr size_t kLdsPerCu = 160 * 1024;
-// scenes up to this many primitives use the flat leaf-list traversal (LM 3)
-constexpr int kFlatMaxPrims = 24;   // flat leaf list up to this many primitives; measured: CBspheres 488 -> 511 Msamples/s, CBspheres_lambertian +6%, CBempty -1%
-constexpr size_t kBlocksPerCu = 4 * kMinWaves / kWavesPerBlock;
-constexpr size_t kLdsSceneMax = kLdsPerCu / kBlocksPerCu - kWavesPerBlock * sizeof(WaveQ) - 256 - kStaticLds;
-// LM 2's treelet gets kLdsSceneMax - kLdsStackBytes (an unsigned difference): it must hold at least
-// one node, or the subtraction wraps and the treelet size is no longer capped by the LDS budget
-static_assert(kLdsSceneMax > kLdsStackBytes + (size_t)node_bytes(lm_width(2)), "LDS budget: wave queues + stack slots leave no treelet");
-
-// Persistent launch: as many blocks as are co-resident (occupancy query with this launch's LDS),
-// never more waves than work items.
-template <class K, class KP>
-int launch_persistent(Ctx* c, K kernel, const char* name, size_t lds, const KP& kp, long long items) {
-  int per_cu = 0;
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, lds));
-  if (per_cu <= 0) { g_err = std::string(name) + " cannot be resident (LDS/VGPR budget)"; return BDPT_E_DEVICE; }
-  long long grid = std::min<long long>((long long)per_cu * c->ncu, (items + kWavesPerBlock - 1) / kWavesPerBlock);
-  grid = std::max(1LL, grid);
-  c->last_plan[2] = (int)lds;
-  c->last_plan[3] = (int)grid;
-  c->last_plan[5] = (int)items;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kBlock), lds, c->stream, kp);
-  HIPCHK(hipGetLastError());
-  return BDPT_OK;
-}
-
-// The block's LDS copy of the scene for a kernel with lds_max bytes for it: the LDS mode
-// (BDPT_LDS_MODE's, else the flat list for tiny scenes, else the whole scene, else the treelet; a
-// mode that does not fit or has nothing to stage falls back 3 -> 1 -> 2 -> 0), the view and node
-// count of that mode, and the bytes of the flat and whole-scene copies. treelet_max: the bytes a
-// treelet may take. Returns the mode.
-template <class KP>
-int pick_lds_copy(Ctx* c, KP& kp, size_t lds_max, size_t treelet_max, size_t* flat, size_t* full) {
-  *full = (c->hs.tree(lm_width(1)).nodes.size() + c->hs.geom.size()) * sizeof(float);
-  const bool has_nodes = !c->hs.bvh2.nodes.empty();
-  // LM 3's LDS: geometry, leaf list (padded to 16 B), shading records
-  *flat = 2 * c->hs.geom.size() * sizeof(float) + (c->hs.leaf_refs.size() + 3) / 4 * 16;
-  int lm = c->env_lds_mode >= 0 ? c->env_lds_mode   // diagnostics: BDPT_LDS_MODE forces 0 / 1 / 2 / 3
-               : (c->hs.nprim <= kFlatMaxPrims && *flat <= lds_max) ? 3
-               : (*full <= lds_max ? 1 : has_nodes ? 2 : 0);
-  if (lm == 3 && *flat > lds_max) lm = 1;
-  if (lm == 1 && *full > lds_max) lm = 2;
-  if (lm == 2 && !has_nodes) lm = 0;
-  kp.S = view_of(c, lm);
-  kp.n_node4 = (int)(c->hs.tree(lm_width(lm)).nodes.size() / 4);
-  if (lm == 2) kp.S.ntop = (int)std::min<size_t>((size_t)c->hs.tree(lm_width(2)).n_top,
-                                                 treelet_max / node_bytes(lm_width(2)));
-  c->last_lm = lm;
-  return lm;
-}
-// the bytes of mode lm's copy
-size_t lds_copy_bytes(int lm, const SceneView& S, size_t flat, size_t full) {
-  return lm == 3 ? flat : lm == 1 ? full : lm == 2 ? (size_t)S.ntop * node_bytes(lm_width(2)) : 0;
-}
-
 // The LDS mode of a BDPT launch and the dynamic LDS it needs (wave queues + the scene copy).
 int pick_lm(Ctx* c, KParams& kp, size_t* lds) {
-  size_t flat, full;
-  const int lm = pick_lds_copy(c, kp, kLdsSceneMax, kLdsSceneMax - kLdsStackBytes, &flat, &full);
-  if (lm == 2 && c->env_ntop_max >= 0) kp.S.ntop = std::min(kp.S.ntop, c->env_ntop_max);   // diagnostics
+  size_t treelet_max = kLdsSceneMax - kLdsStackBytes;
+  if (c->env_ntop_max >= 0)   // diagnostics: BDPT_NTOP_MAX caps the treelet's nodes
+    treelet_max = std::min(treelet_max, (size_t)c->env_ntop_max * node_bytes(lm_width(2)));
+  const LdsPlan p = lds_plan(c->hs, c->env_lds_mode, kLdsSceneMax, treelet_max);
+  apply_plan(c, p, kp);
   // LM 2 always gives the stacks their LDS slots (the treelet makes room); LM 1 when the whole
   // scene and the slots fit together (CBgems: +0.5 .. +0.8 %, profiles/r04o_ab_stack_lm1.log)
-  kp.lstack_on = lm == 2 || (lm == 1 && full + kLdsStackBytes <= kLdsSceneMax);
-  *lds = kWavesPerBlock * sizeof(WaveQ) + (kp.lstack_on ? kLdsStackBytes : 0) + lds_copy_bytes(lm, kp.S, flat, full);
-  return lm;
+  kp.lstack_on = p.lm == 2 || (p.lm == 1 && p.full_bytes + kLdsStackBytes <= kLdsSceneMax);
+  *lds = kWavesPerBlock * sizeof(WaveQ) + (kp.lstack_on ? kLdsStackBytes : 0) + p.copy_bytes;
+  return p.lm;
 }
 
 // Whether k_bdpt_sample copies the materials and lights to its static LDS arrays: the predicate
 // stage_scene evaluates, on the host for bdpt_debug_launch_plan.
 bool mats_lights_staged(const KParams& kp) { return kp.nmat <= kLdsMats && kp.S.nlights <= kLdsLights; }
+
+// launch_persistent for the LDS mode lm, on record as the context's last launch
+// (bdpt_debug_launch_plan, bdpt_stats.lds_mode). launch(LM, grid_out) is the launch_persistent call.
+template <class F>
+int launch_recorded(Ctx* c, int lm, size_t lds, long long items, F&& launch) {
+  int grid = 0;
+  c->last_lm = lm;
+  const int rc = dispatch_lm(lm, [&](auto LM) { return launch(LM, &grid); });
+  if (grid > 0) {
+    c->last_plan[2] = (int)lds;
+    c->last_plan[3] = grid;
+    c->last_plan[5] = (int)items;
+  }
+  return rc;
+}
 
 template <int MAXV, bool STATS, int EXT>
 int launch_lm(Ctx* c, KParams& kp) {
@@ -177,10 +135,9 @@ int launch_lm(Ctx* c, KParams& kp) {
   c->last_plan[1] = kp.S.ntop;
   c->last_plan[4] = kp.spl;
   c->last_plan[6] = mats_lights_staged(kp) ? 1 : 0;
-  if (lm == 3) return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 3, EXT>, "k_bdpt_sample", lds, kp, kp.nitems);
-  if (lm == 1) return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 1, EXT>, "k_bdpt_sample", lds, kp, kp.nitems);
-  if (lm == 2) return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 2, EXT>, "k_bdpt_sample", lds, kp, kp.nitems);
-  return launch_persistent(c, k_bdpt_sample<MAXV, STATS, 0, EXT>, "k_bdpt_sample", lds, kp, kp.nitems);
+  return launch_recorded(c, lm, lds, kp.nitems, [&](auto LM, int* grid) {
+    return launch_persistent(c, k_bdpt_sample<MAXV, STATS, decltype(LM)::value, EXT>, "k_bdpt_sample", lds, kp, kp.nitems, grid);
+  });
 }
 
 template <int MAXV>
@@ -194,17 +151,14 @@ int launch_maxv(Ctx* c, KParams& kp) {
 
 template <bool STATS>
 int launch_pt(Ctx* c, PtKParams& kp) {
-  const size_t lds_max = kLdsPerCu / kBlocksPerCu - 256;   // k_pt's LDS holds the scene copy only
-  size_t flat, full;
-  const int lm = pick_lds_copy(c, kp, lds_max, lds_max, &flat, &full);
+  const LdsPlan p = lds_plan(c->hs, c->env_lds_mode, kLdsCopyOnlyMax, kLdsCopyOnlyMax);
+  apply_plan(c, p, kp);
   kp.n_geom4 = (int)(c->hs.geom.size() / 4);
-  const size_t lds = lds_copy_bytes(lm, kp.S, flat, full);
   c->last_plan[0] = c->last_plan[4] = c->last_plan[6] = -1;   // k_pt: no stack slots, chunks or material copy
   c->last_plan[1] = kp.S.ntop;
-  if (lm == 3) return launch_persistent(c, k_pt<STATS, 3>, "k_pt", lds, kp, kp.nblocks);
-  if (lm == 1) return launch_persistent(c, k_pt<STATS, 1>, "k_pt", lds, kp, kp.nblocks);
-  if (lm == 2) return launch_persistent(c, k_pt<STATS, 2>, "k_pt", lds, kp, kp.nblocks);
-  return launch_persistent(c, k_pt<STATS, 0>, "k_pt", lds, kp, kp.nblocks);
+  return launch_recorded(c, p.lm, p.copy_bytes, kp.nblocks, [&](auto LM, int* grid) {
+    return launch_persistent(c, k_pt<STATS, decltype(LM)::value>, "k_pt", p.copy_bytes, kp, kp.nblocks, grid);
+  });
 }
 
 void free_ctx(Ctx* c) {
@@ -335,14 +289,10 @@ int bdpt_create(const bdpt_scene_desc* scene, const bdpt_params* params, void** 
   if (c->hs.env_light >= 0 && (rc = upload(&c->d_env, c->hs.env))) return fail(rc);
   c->npix = (size_t)p.width * p.height;
   size_t fb = c->npix * 3 * sizeof(float);
-  if (hipMalloc((void**)&c->d_eye, fb) != hipSuccess || hipMalloc((void**)&c->d_light, fb) != hipSuccess ||
-      hipMalloc((void**)&c->d_sample, fb) != hipSuccess ||
-      hipMalloc((void**)&c->d_count, c->npix * sizeof(int)) != hipSuccess ||
-      hipMalloc((void**)&c->d_work8, 8 * 32 * sizeof(unsigned)) != hipSuccess ||
-      hipMalloc((void**)&c->d_stats, Ctx::kStatSlots * sizeof(unsigned long long)) != hipSuccess) {
-    g_err = "out of device memory";
-    return fail(BDPT_E_NOMEM);
-  }
+  if ((rc = ensure_alloc(&c->d_eye, fb)) || (rc = ensure_alloc(&c->d_light, fb)) || (rc = ensure_alloc(&c->d_sample, fb)) ||
+      (rc = ensure_alloc(&c->d_count, c->npix * sizeof(int))) || (rc = ensure_alloc(&c->d_work8, 8 * 32 * sizeof(unsigned))) ||
+      (rc = ensure_alloc(&c->d_stats, Ctx::kStatSlots * sizeof(unsigned long long))))
+    return fail(rc);
   bool ev_ok = true;
   for (Ctx::BlockSlot& b : c->blk) ev_ok = ev_ok && hipEventCreateWithFlags(&b.done, hipEventDisableTiming) == hipSuccess;
   if (!ev_ok || hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking) != hipSuccess ||
@@ -351,11 +301,8 @@ int bdpt_create(const bdpt_scene_desc* scene, const bdpt_params* params, void** 
     return fail(BDPT_E_DEVICE);
   }
   c->stream = c->own;
-  if (hipMemsetAsync(c->d_eye, 0, fb, c->stream) != hipSuccess ||
-      hipMemsetAsync(c->d_light, 0, fb, c->stream) != hipSuccess ||
-      hipMemsetAsync(c->d_count, 0, c->npix * sizeof(int), c->stream) != hipSuccess ||
-      hipMemsetAsync(c->d_stats, 0, Ctx::kStatSlots * sizeof(unsigned long long), c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess) { g_err = "init sync failed"; return fail(BDPT_E_DEVICE); }
+  // the frames, the sample counts and the stat slots start at zero, as after bdpt_clear
+  if (bdpt_clear(c) != BDPT_OK || hipStreamSynchronize(c->stream) != hipSuccess) { g_err = "init sync failed"; return fail(BDPT_E_DEVICE); }
   *ctx_out = c;
   return BDPT_OK;
 }
@@ -420,14 +367,8 @@ int bdpt_render(void* ctx, const bdpt_tile* tiles, int32_t ntiles, int32_t spp_b
   int nblocks = 0;
   Ctx::BlockSlot* slot = nullptr;
   if (tiles && ntiles > 0) {
-    // Tiles (raytrace_tile clips them to the frame, raytraced_renderer.cpp:600-604) -> 8x8 blocks.
     std::vector<int4> blk;
-    for (int t = 0; t < ntiles; t++) {
-      int x0 = std::max(0, tiles[t].x0), y0 = std::max(0, tiles[t].y0);
-      int x1 = std::min(W, tiles[t].x0 + tiles[t].w), y1 = std::min(H, tiles[t].y0 + tiles[t].h);
-      for (int by = y0; by < y1; by += 8)
-        for (int bx = x0; bx < x1; bx += 8) blk.push_back(make_int4(bx, by, std::min(8, x1 - bx), std::min(8, y1 - by)));
-    }
+    tiles_to_blocks(tiles, ntiles, W, H, blk);
     if (blk.empty()) return BDPT_OK;
     // next slot of the staging ring: wait only for the launch that last read it
     slot = &c->blk[c->blk_next];
@@ -477,13 +418,9 @@ int bdpt::render_blocks(Ctx* c, const int4* d_blocks, int nblocks, int spp_begin
   kp.nmat = (int)c->hs.mats.size();
   kp.item_lo = 0;
   kp.lstack_on = 0;
-  kp.blocks = nullptr;
+  kp.blocks = d_blocks;
   kp.nbx = (W + 7) / 8;
-  kp.nblocks = kp.nbx * ((H + 7) / 8);
-  if (d_blocks) {
-    kp.blocks = d_blocks;
-    kp.nblocks = nblocks;
-  }
+  kp.nblocks = d_blocks ? nblocks : kp.nbx * ((H + 7) / 8);
   if (c->pt) {   // the PathTracer renders whole pixels (adaptive sampling decides per pixel)
     if (spp_begin != 0 || spp_count != c->prm.spp) {
       g_err = "the PathTracer renders whole pixels: spp_begin must be 0 and spp_count the ctx's spp";
@@ -497,15 +434,14 @@ int bdpt::render_blocks(Ctx* c, const int4* d_blocks, int nblocks, int spp_begin
     pk.pp.hemisphere = c->prm.direct_hemisphere_sample != 0;
     pk.pp.tol = c->prm.max_tolerance;
     pk.pp.lens_radius = (float)c->prm.lens_radius;
-    pk.pp.focal_distance = (float)(c->prm.focal_distance > 0 ? c->prm.focal_distance : 4.7);
+    pk.pp.focal_distance = pt_focal(c->prm);
     pk.eye = c->d_eye;
     pk.count = c->d_count;
     pk.stats = c->d_stats;
     pk.blocks = kp.blocks;
     pk.nblocks = kp.nblocks;
     pk.nbx = kp.nbx;
-    pk.work = (unsigned*)(c->d_stats + 15);
-    HIPCHK(hipMemsetAsync(pk.work, 0, sizeof(unsigned), c->stream));
+    if (!(pk.work = reset_tickets(c))) return BDPT_E_DEVICE;
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     int rc = c->prm.collect_stats ? launch_pt<true>(c, pk) : launch_pt<false>(c, pk);
     if (rc) return rc;
@@ -532,8 +468,7 @@ int bdpt::render_blocks(Ctx* c, const int4* d_blocks, int nblocks, int spp_begin
   // consecutive tickets take one pixel block's sample chunks in turn (measured: C2 +1.2%, CBgems
   // +2%, Lucy stand-in 1080p +-0 over chunk-major order); BDPT_BLOCK_MAJOR=0 restores chunk-major
   kp.block_major = c->block_major;
-  kp.work = (unsigned*)(c->d_stats + 15);
-  HIPCHK(hipMemsetAsync(kp.work, 0, sizeof(unsigned), c->stream));
+  if (!(kp.work = reset_tickets(c))) return BDPT_E_DEVICE;
   kp.work8 = c->d_work8;
   kp.region = (kp.nitems + 7u) / 8u;
   kp.xcd = c->xcd;
@@ -667,25 +602,19 @@ int bdpt_get_stats(void* ctx, bdpt_stats* out) {
   return BDPT_OK;
 }
 
-int bdpt_debug_lane_counters(void* ctx, uint64_t* out16) {
+// 16 of the stat slots (Ctx::d_stats) from slot `first` on, once the stream has drained.
+static int read_stat_slots(void* ctx, int first, uint64_t* out16) {
   Ctx* c = (Ctx*)ctx;
   if (!c || !out16) { g_err = "null argument"; return BDPT_E_INVALID; }
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipMemcpy(out16, c->d_stats + 32, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out16, c->d_stats + first, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return BDPT_OK;
 }
 
-int bdpt_debug_counters(void* ctx, uint64_t* out16) {
-  Ctx* c = (Ctx*)ctx;
-  if (!c || !out16) { g_err = "null argument"; return BDPT_E_INVALID; }
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipMemcpy(out16, c->d_stats + 16, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return BDPT_OK;
-}
+int bdpt_debug_lane_counters(void* ctx, uint64_t* out16) { return read_stat_slots(ctx, 32, out16); }
+int bdpt_debug_counters(void* ctx, uint64_t* out16) { return read_stat_slots(ctx, 16, out16); }
 
 int bdpt_debug_launch_plan(void* ctx, int32_t* out8) {
   Ctx* c = (Ctx*)ctx;

@@ -7,19 +7,17 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
 #include <mutex>
 #include <string>
 
 #include "bdpt/bdpt.h"
-#include "bdpt_ctx.h"
+#include "bdpt_launch.h"   // bdpt_ctx.h
+#include "bdpt_tile.h"
 #include "bdpt_variance.h"
 
 using namespace bdpt;
 
 namespace {
-
-constexpr int kLinBlock = 256;
 
 // One lane per pixel, linear over the frame: the record is one 16-byte load and one 16-byte store.
 // b == nullptr: the cumulative colour is a alone; else a + b, added as k_combine adds them.
@@ -37,21 +35,10 @@ __global__ __launch_bounds__(kLinBlock) void k_variance(const float4* rec, float
   var[i] = variance_of(rec[i], kf);
 }
 
-// The filter. k_atrous's shape (bdpt_denoise.hip): one launch per level, a wave owns an 8x8 pixel
-// tile (lane = pixel), four tiles per 256-thread block, no LDS: the 9 prefilter taps lie in the tile
-// and its rim, which the level's own 25 variance taps at step 1 read anyway, and from step 4 on
-// neighbouring tiles share no taps; the frames sit in L2 / the Infinity Cache.
-constexpr int kAtrousBlock = 256;
-
-__device__ __forceinline__ bool tile_pixel(int W, int H, int& x, int& y) {
-  const int ntx = (W + 7) / 8;
-  const long long tile = (long long)blockIdx.x * (kAtrousBlock / 64) + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  x = (int)(tile % ntx) * 8 + (lane & 7);
-  y = (int)(tile / ntx) * 8 + (lane >> 3);
-  return x < W && y < H;
-}
-
+// The filter. k_atrous's shape (bdpt_denoise.hip): one launch per level over the wave tiles of
+// bdpt_tile.h, no LDS: the 9 prefilter taps lie in the tile and its rim, which the level's own 25
+// variance taps at step 1 read anyway, and from step 4 on neighbouring tiles share no taps; the
+// frames sit in L2 / the Infinity Cache.
 __global__ __launch_bounds__(kAtrousBlock) void k_atrous_var(const float* c_in, const float* v_in, const float* F,
                                                              float* c_out, float* v_out, AtrousLevel L) {
   int x, y;
@@ -91,16 +78,13 @@ int check_params(const bdpt_denoise_variance_params* p, bdpt_denoise_variance_pa
   return BDPT_OK;
 }
 
-unsigned lin_grid(size_t npix) { return (unsigned)((npix + kLinBlock - 1) / kLinBlock); }
-
 // Enqueues the filter: (color, var) -> (out, var_out or nowhere) through two scratch pairs (sc[k]
 // W*H*3, sv[k] W*H). Level i reads the current pair and writes pair i & 1; the last pass copies to
 // out, so out may be color (and var_out var). levels == 0 is that copy alone.
 int enqueue_filter(hipStream_t st, const float* color, const float* var, const float* F, int W, int H,
                    const bdpt_denoise_variance_params& p, float* out, float* var_out, float* sc0, float* sc1, float* sv0,
                    float* sv1) {
-  const long long tiles = (long long)((W + 7) / 8) * ((H + 7) / 8);
-  const dim3 grid((unsigned)((tiles + kAtrousBlock / 64 - 1) / (kAtrousBlock / 64))), block(kAtrousBlock);
+  const dim3 grid = tile_grid(W, H), block(kAtrousBlock);
   float* sc[2] = {sc0, sc1};
   float* sv[2] = {sv0, sv1};
   const float* cur = color;
@@ -154,14 +138,11 @@ int bdpt_render_batches(void* ctx, int32_t spp_begin, int32_t spp_count, int32_t
     return BDPT_E_INVALID;
   }
   HIPCHK(hipSetDevice(c->device));
-  if (!c->d_moments) {
-    if (hipMalloc((void**)&c->d_moments, c->npix * sizeof(float4)) != hipSuccess) { g_err = "out of device memory"; return BDPT_E_NOMEM; }
-    HIPCHK(hipMemsetAsync(c->d_moments, 0, c->npix * sizeof(float4), c->stream));
-  }
+  int rc = ensure_alloc(&c->d_moments, c->npix * sizeof(float4), &c->stream);
+  if (rc) return rc;
   BatchScope scope(c);
   for (int k = 0; k < batches; k++) {
-    const int rc = bdpt_render(ctx, nullptr, 0, spp_begin + k * per, per);
-    if (rc) return rc;
+    if ((rc = bdpt_render(ctx, nullptr, 0, spp_begin + k * per, per))) return rc;
     hipLaunchKernelGGL(k_moments, dim3(lin_grid(c->npix)), dim3(kLinBlock), 0, c->stream, c->d_eye, c->d_light,
                        (float4*)c->d_moments, (long long)c->npix);
     HIPCHK(hipGetLastError());
@@ -179,7 +160,8 @@ int bdpt_variance(void* ctx) {
   if (c->var_unbatched) { g_err = "bdpt_variance: the frame holds samples that were not rendered in batches"; return BDPT_E_INVALID; }
   if (c->var_batches < 2) { g_err = "bdpt_variance needs at least 2 batches (bdpt_render_batches)"; return BDPT_E_INVALID; }
   HIPCHK(hipSetDevice(c->device));
-  if (!c->d_variance && hipMalloc((void**)&c->d_variance, c->npix * sizeof(float)) != hipSuccess) { g_err = "out of device memory"; return BDPT_E_NOMEM; }
+  const int rc = ensure_alloc(&c->d_variance, c->npix * sizeof(float));
+  if (rc) return rc;
   hipLaunchKernelGGL(k_variance, dim3(lin_grid(c->npix)), dim3(kLinBlock), 0, c->stream, (const float4*)c->d_moments,
                      c->d_variance, (long long)c->npix, var_k(c->var_batches));
   HIPCHK(hipGetLastError());
@@ -187,35 +169,14 @@ int bdpt_variance(void* ctx) {
   return BDPT_OK;
 }
 
-int bdpt_read_variance(void* ctx, float* var) {
-  Ctx* c = (Ctx*)ctx;
-  if (!c || !var) { g_err = "null argument"; return BDPT_E_INVALID; }
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  if (!c->variance_valid) { g_err = "no variance frame on this context (bdpt_variance)"; return BDPT_E_INVALID; }
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(var, c->d_variance, c->npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BDPT_OK;
-}
+static float* variance_of(Ctx* c) { return c->variance_valid ? c->d_variance : nullptr; }
+static float* moments_of(Ctx* c) { return c->d_moments; }
+static const char* const kNoVariance = "no variance frame on this context (bdpt_variance)";
 
-int bdpt_variance_device_ptr(void* ctx, void** dptr) {
-  Ctx* c = (Ctx*)ctx;
-  if (!c || !dptr) { g_err = "null argument"; return BDPT_E_INVALID; }
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  if (!c->variance_valid) { g_err = "no variance frame on this context (bdpt_variance)"; return BDPT_E_INVALID; }
-  *dptr = c->d_variance;
-  return BDPT_OK;
-}
-
+int bdpt_read_variance(void* ctx, float* var) { return frame_out(ctx, variance_of, kNoVariance, sizeof(float), var, nullptr); }
+int bdpt_variance_device_ptr(void* ctx, void** dptr) { return frame_out(ctx, variance_of, kNoVariance, 0, nullptr, dptr); }
 int bdpt_read_moments(void* ctx, float* rec4) {
-  Ctx* c = (Ctx*)ctx;
-  if (!c || !rec4) { g_err = "null argument"; return BDPT_E_INVALID; }
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  if (!c->d_moments) { g_err = "no moments record on this context (bdpt_render_batches)"; return BDPT_E_INVALID; }
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(rec4, c->d_moments, c->npix * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BDPT_OK;
+  return frame_out(ctx, moments_of, "no moments record on this context (bdpt_render_batches)", sizeof(float4), rec4, nullptr);
 }
 
 int bdpt_denoise_variance(void* ctx, const bdpt_denoise_variance_params* p) {
@@ -229,9 +190,9 @@ int bdpt_denoise_variance(void* ctx, const bdpt_denoise_variance_params* p) {
   if (!c->variance_valid) { g_err = "bdpt_denoise_variance needs a variance frame first (bdpt_variance)"; return BDPT_E_INVALID; }
   HIPCHK(hipSetDevice(c->device));
   const size_t fb = c->npix * 3 * sizeof(float);
-  if (!c->d_denoised && hipMalloc((void**)&c->d_denoised, fb) != hipSuccess) { g_err = "out of device memory"; return BDPT_E_NOMEM; }
-  if (!c->d_dn_scratch && hipMalloc((void**)&c->d_dn_scratch, 2 * fb) != hipSuccess) { g_err = "out of device memory"; return BDPT_E_NOMEM; }
-  if (!c->d_var_scratch && hipMalloc((void**)&c->d_var_scratch, 2 * c->npix * sizeof(float)) != hipSuccess) { g_err = "out of device memory"; return BDPT_E_NOMEM; }
+  if ((rc = ensure_alloc(&c->d_denoised, fb)) || (rc = ensure_alloc(&c->d_dn_scratch, 2 * fb)) ||
+      (rc = ensure_alloc(&c->d_var_scratch, 2 * c->npix * sizeof(float))))
+    return rc;
   void* src = nullptr;
   if ((rc = bdpt_frame_device_ptr(ctx, BDPT_FRAME_SAMPLE, &src))) return rc;
   rc = enqueue_filter(c->stream, (const float*)src, c->d_variance, c->d_features, c->prm.width, c->prm.height, dp, c->d_denoised,
@@ -244,9 +205,9 @@ int bdpt_denoise_variance(void* ctx, const bdpt_denoise_variance_params* p) {
 int bdpt_moments_buffers(int32_t device, const float* d_frame_a, const float* d_frame_b, float* d_record, int32_t w, int32_t h,
                          void* stream) {
   if (!d_frame_a || !d_record) { g_err = "null argument"; return BDPT_E_INVALID; }
-  if (w <= 0 || h <= 0) { g_err = "invalid frame size"; return BDPT_E_INVALID; }
-  if (((uintptr_t)d_record & 15u) != 0) { g_err = "d_record must be 16-byte aligned"; return BDPT_E_INVALID; }
-  if (device < 0) { g_err = "bad device ordinal"; return BDPT_E_INVALID; }
+  const int rc = check_frame(device, w, h);
+  if (rc) return rc;
+  if (!aligned16(d_record)) { g_err = "d_record must be 16-byte aligned"; return BDPT_E_INVALID; }
   HIPCHK(hipSetDevice(device));
   const size_t npix = (size_t)w * h;
   hipLaunchKernelGGL(k_moments, dim3(lin_grid(npix)), dim3(kLinBlock), 0, (hipStream_t)stream, d_frame_a, d_frame_b,
@@ -258,10 +219,10 @@ int bdpt_moments_buffers(int32_t device, const float* d_frame_a, const float* d_
 int bdpt_variance_buffers(int32_t device, const float* d_record, int32_t batches, int32_t w, int32_t h, float* d_var,
                           void* stream) {
   if (!d_record || !d_var) { g_err = "null argument"; return BDPT_E_INVALID; }
-  if (w <= 0 || h <= 0) { g_err = "invalid frame size"; return BDPT_E_INVALID; }
+  const int rc = check_frame(device, w, h);
+  if (rc) return rc;
   if (batches < 2) { g_err = "a variance needs at least 2 batches"; return BDPT_E_INVALID; }
-  if (((uintptr_t)d_record & 15u) != 0) { g_err = "d_record must be 16-byte aligned"; return BDPT_E_INVALID; }
-  if (device < 0) { g_err = "bad device ordinal"; return BDPT_E_INVALID; }
+  if (!aligned16(d_record)) { g_err = "d_record must be 16-byte aligned"; return BDPT_E_INVALID; }
   HIPCHK(hipSetDevice(device));
   const size_t npix = (size_t)w * h;
   hipLaunchKernelGGL(k_variance, dim3(lin_grid(npix)), dim3(kLinBlock), 0, (hipStream_t)stream, (const float4*)d_record, d_var,
@@ -274,12 +235,11 @@ int bdpt_denoise_variance_buffers(int32_t device, const float* d_color, const fl
                                   int32_t h, const bdpt_denoise_variance_params* p, float* d_out, float* d_var_out,
                                   void* stream) {
   if (!d_color || !d_var || !d_features || !d_out) { g_err = "null argument"; return BDPT_E_INVALID; }
-  if (w <= 0 || h <= 0) { g_err = "invalid frame size"; return BDPT_E_INVALID; }
-  if (((uintptr_t)d_features & 15u) != 0) { g_err = "d_features must be 16-byte aligned"; return BDPT_E_INVALID; }
-  bdpt_denoise_variance_params dp;
-  int rc = check_params(p, &dp);
+  int rc = check_frame(device, w, h);
   if (rc) return rc;
-  if (device < 0) { g_err = "bad device ordinal"; return BDPT_E_INVALID; }
+  if (!aligned16(d_features)) { g_err = "d_features must be 16-byte aligned"; return BDPT_E_INVALID; }
+  bdpt_denoise_variance_params dp;
+  if ((rc = check_params(p, &dp))) return rc;
   HIPCHK(hipSetDevice(device));
   const size_t n = (size_t)w * h;
   float* scratch = nullptr;

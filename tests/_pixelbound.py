@@ -130,6 +130,8 @@ def _core():
                                             _IP, _IP, _FP, _IP, _FP, _IP, _FP, C.POINTER(C.c_longlong),
                                             C.POINTER(C.c_longlong), _FP]
         lib.core_cpu_lds_facts.argtypes = [C.POINTER(B.SceneDesc), C.c_int, _IP]
+        lib.core_cpu_lds_plan.argtypes = [C.POINTER(B.SceneDesc), C.c_int, C.c_int, C.c_longlong, C.c_longlong,
+                                          C.POINTER(C.c_longlong)]
         _rec_ready = True
     return lib
 
@@ -210,6 +212,17 @@ def lds_facts(scene, infinite_lights=False):
     f = dict(zip(("nprim", "full", "flat", "n_top", "node_bytes", "nmat", "nlights", "flat_n"), list(out)))
     f["cap"] = (LDS_SCENE_MAX - LDS_STACK_BYTES) // f["node_bytes"]
     return f
+
+
+def lds_plan(scene, forced_lm=-1, lds_max=LDS_SCENE_MAX, treelet_max=LDS_SCENE_MAX - LDS_STACK_BYTES, infinite_lights=False):
+    """lds_plan (csrc/bdpt_ldsplan.h) on build_host_scene's scene: {"lm", "ntop", "n_node4", "copy_bytes",
+    "flat_bytes", "full_bytes"}. The default budgets are a BDPT launch's. scene None: the host scene with
+    no primitives."""
+    out = (C.c_longlong * 6)()
+    d = scene.desc() if scene is not None else None
+    assert _core().core_cpu_lds_plan(C.byref(d) if d is not None else None, 1 if infinite_lights else 0, forced_lm,
+                                     lds_max, treelet_max, out) == 0
+    return dict(zip(("lm", "ntop", "n_node4", "copy_bytes", "flat_bytes", "full_bytes"), list(out)))
 
 
 # ------------------------------------------------------------------------------------------------

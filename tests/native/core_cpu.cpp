@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "bdpt_core.h"
+#include "bdpt_ldsplan.h"
 #include "bdpt_scene.h"
 
 using namespace bdpt;
@@ -203,7 +204,7 @@ extern "C" int core_cpu_render_rec(const bdpt_scene_desc* d, int W, int H, int s
   return rc;
 }
 
-// What the LDS plan of a launch is chosen from (bdpt_hip.hip pick_lds_copy / pick_lm), from the same
+// What the LDS plan of a launch is chosen from (bdpt_ldsplan.h lds_plan), from the same
 // build_host_scene: out8 = {primitive records, bytes of the whole-scene copy (binary tree + geometry),
 // bytes of the flat-list copy, the 4-wide tree's BFS treelet candidates (n_top), bytes of one 4-wide
 // node, materials, lights, the flat list's length or 0}. infinite_lights: bdpt_params.infinite_lights.
@@ -212,15 +213,30 @@ extern "C" int core_cpu_lds_facts(const bdpt_scene_desc* d, int infinite_lights,
   std::string err;
   int rc = build_host_scene(d, hs, err, false, infinite_lights != 0);
   if (rc) return rc;
+  const LdsPlan p = lds_plan(hs, -1, 0, 0);   // the two byte counts do not depend on the budget
   out8[0] = hs.nprim;
-  out8[1] = (int)((hs.tree(lm_width(1)).nodes.size() + hs.geom.size()) * sizeof(float));
-  out8[2] = (int)(2 * hs.geom.size() * sizeof(float) + (hs.leaf_refs.size() + 3) / 4 * 16);
+  out8[1] = (int)p.full_bytes;
+  out8[2] = (int)p.flat_bytes;
   out8[3] = hs.tree(lm_width(2)).n_top;
   out8[4] = node_bytes(lm_width(2));
   out8[5] = (int)hs.mats.size();
   out8[6] = (int)hs.lights.size();
   uint32_t sph = 0;
   out8[7] = flat_prims(hs, &sph);
+  return 0;
+}
+
+// lds_plan itself: out6 = {lm, ntop, n_node4, copy_bytes, flat_bytes, full_bytes}. forced_lm: -1 = none.
+// d == null: the HostScene with no primitives (build_host_scene refuses a description of one).
+extern "C" int core_cpu_lds_plan(const bdpt_scene_desc* d, int infinite_lights, int forced_lm, long long lds_max,
+                                 long long treelet_max, long long* out6) {
+  HostScene hs;
+  std::string err;
+  const int rc = d ? build_host_scene(d, hs, err, false, infinite_lights != 0) : 0;
+  if (rc) return rc;
+  const LdsPlan p = lds_plan(hs, forced_lm, (size_t)lds_max, (size_t)treelet_max);
+  out6[0] = p.lm; out6[1] = p.ntop; out6[2] = p.n_node4;
+  out6[3] = (long long)p.copy_bytes; out6[4] = (long long)p.flat_bytes; out6[5] = (long long)p.full_bytes;
   return 0;
 }
 

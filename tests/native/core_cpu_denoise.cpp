@@ -70,7 +70,7 @@ int setup(const bdpt_scene_desc* d, int W, int H, int nsamp, uint64_t seed, int 
   if (pt) {
     s.fp.kind = FEAT_PT;
     s.fp.lens_r = (float)lens_radius;
-    s.fp.focal = (float)(focal_distance > 0 ? focal_distance : 4.7);
+    s.fp.focal = lens_focal(focal_distance);
   } else {
     s.fp.kind = kernel_flavour(s.hs, false, lens) == 3 ? FEAT_BDPT_LENS : FEAT_BDPT;
     s.fp.lens_r = 0.0f;

@@ -2,8 +2,8 @@
 tests/_pixelbound.py of the CPU build of the same device code (bit-equal to oracle mode 2,
 tests/test_core_cpu.py), with no pixel allowed outside — over the launch shapes, LDS plans, staging
 branches and depth classes of k_bdpt_sample that only the GPU executes (bdpt_hip.hip: next_item /
-block_pixel, connect_sample, flush_queue, finish_item, stage_scene, pick_lm, launch_persistent, the
-tile cutting of bdpt_render), each case asserting the launch plan (bdpt_debug_launch_plan) or the
+block_pixel, connect_sample, flush_queue, finish_item, stage_scene, pick_lm; bdpt_launch.h:
+launch_persistent, tiles_to_blocks), each case asserting the launch plan (bdpt_debug_launch_plan) or the
 scene facts that prove it ran the branch it names. k_pt, which has no atomics, is held bit-exact.
 The bound's soundness and sharpness: tests/test_pixel_bounds.py (CPU)."""
 import functools
@@ -159,6 +159,7 @@ TILES = {
     "clipped": [(30, 20, 32, 32)],
     "negative_origin": [(-4, -4, 10, 10)],
     "corners": [(0, 0, 1, 1), (TW - 1, 0, 1, 1), (0, TH - 1, 1, 1), (TW - 1, TH - 1, 1, 1)],
+    "far_edge_past_int32": [(8, 0, 2**31 - 1, 8)],   # x0 + w > INT32_MAX: clipped to the frame like any other
 }
 
 
@@ -172,7 +173,7 @@ def _tile_pixels(tiles):
 @pytest.mark.parametrize("key", list(TILES))
 def test_tiles(key):
     """Tiles on a 37x29 frame cut into pixel blocks: unaligned, clipped at the right and top edges,
-    with a negative origin, and 1x1 tiles at the four corners. Inside the tiles the eye frame obeys
+    with a negative origin, 1x1 tiles at the four corners, and one whose x0 + w passes INT32_MAX. Inside the tiles the eye frame obeys
     the bound, outside it is exactly 0 (the reference is 0 there); the light frame obeys the bound
     against a CPU-build render of the same pixel list."""
     M = 5

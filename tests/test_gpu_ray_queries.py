@@ -98,7 +98,7 @@ def _oracle_frame(rname):
     return _renders[rname]
 
 
-# BDPT_LDS_MODE -> the mode pick_lds_copy (bdpt_hip.hip) runs a one-leaf scene in: unset = the flat
+# BDPT_LDS_MODE -> the mode lds_plan (bdpt_ldsplan.h) runs a one-leaf scene in: unset = the flat
 # list (<= 24 primitives); a forced 2 has no binary nodes to stage and falls to 0
 LEAF_ROOT_MODES = [(None, 3), ("0", 0), ("1", 1), ("2", 0), ("3", 3)]
 

@@ -220,3 +220,74 @@ def test_the_launch_plan_facts_of_the_suite_scenes():
     g = PB.lds_facts(golden_scene("CBgems", 32, 24))
     assert g["full"] == 21760 and g["full"] + PB.LDS_STACK_BYTES <= PB.LDS_SCENE_MAX
     assert g["cap"] == 202 and g["node_bytes"] == 128
+
+
+# ------------------------------------------------------------------------------------------------
+# the LDS plan (csrc/bdpt_ldsplan.h lds_plan), which the launches of k_bdpt_sample, k_pt and k_features share
+
+def _plan_is(p, f, lm, ntop=0):
+    """The plan is mode lm with the copy, the tree and the byte counts that belong to it."""
+    copy = {3: f["flat"], 1: f["full"], 2: ntop * f["node_bytes"], 0: 0}[lm]
+    assert (p["lm"], p["ntop"], p["copy_bytes"]) == (lm, ntop, copy), p
+    assert (p["flat_bytes"], p["full_bytes"]) == (f["flat"], f["full"]), p
+
+
+def test_lds_plan_flat_list_and_its_fallbacks():
+    """CBspheres: the flat list unforced; a forced flat list that misses the budget by a byte falls to the
+    whole scene; a forced whole scene that misses it by a byte falls to the treelet."""
+    sc = golden_scene("CBspheres", 32, 24)
+    f = PB.lds_facts(sc)
+    assert f["nprim"] <= PB.FLAT_MAX_PRIMS and f["flat"] <= PB.LDS_SCENE_MAX and f["n_top"] >= 1
+    _plan_is(PB.lds_plan(sc), f, 3)
+    assert PB.lds_plan(sc)["copy_bytes"] == f["flat"]
+    assert f["flat"] - 1 >= f["full"]   # or the next case would fall through mode 1 as well
+    _plan_is(PB.lds_plan(sc, forced_lm=3, lds_max=f["flat"] - 1), f, 1)
+    tmax = PB.LDS_SCENE_MAX - PB.LDS_STACK_BYTES
+    want = min(f["n_top"], tmax // f["node_bytes"])
+    assert want >= 1
+    _plan_is(PB.lds_plan(sc, forced_lm=1, lds_max=f["full"] - 1, treelet_max=tmax), f, 2, want)
+    # a treelet budget of one node and a bit: one node
+    _plan_is(PB.lds_plan(sc, forced_lm=1, lds_max=f["full"] - 1, treelet_max=2 * f["node_bytes"] - 1), f, 2, 1)
+
+
+def test_lds_plan_whole_scene():
+    """CBgems: too many primitives for the flat list, 21,760 B of tree and geometry: the whole scene."""
+    sc = golden_scene("CBgems", 32, 24)
+    f = PB.lds_facts(sc)
+    assert f["nprim"] > PB.FLAT_MAX_PRIMS and f["full"] == 21760
+    p = PB.lds_plan(sc)
+    _plan_is(p, f, 1)
+    assert p["full_bytes"] == 21760
+
+
+def test_lds_plan_treelet_capped_by_its_budget():
+    """The relief box of 812 triangles is larger than the budget: the treelet, of every BFS candidate
+    when they fit, of treelet_max // node_bytes nodes when they do not."""
+    sc = PB.box_scene(48, 36, 20, 6, area_light=True)
+    f = PB.lds_facts(sc)
+    assert f["full"] > PB.LDS_SCENE_MAX and f["nprim"] > PB.FLAT_MAX_PRIMS and 3 < f["n_top"] < f["cap"]
+    _plan_is(PB.lds_plan(sc), f, 2, f["n_top"])
+    _plan_is(PB.lds_plan(sc, treelet_max=3 * f["node_bytes"] + 5), f, 2, 3)
+    _plan_is(PB.lds_plan(sc, treelet_max=0), f, 2, 0)
+    # k_pt's and k_features' budget (no wave queues, no stack slots): 160 KB / 4 blocks - 256 B
+    copy_only = 160 * 1024 // 4 - 256
+    assert f["full"] > copy_only
+    _plan_is(PB.lds_plan(sc, lds_max=copy_only, treelet_max=copy_only), f, 2, min(f["n_top"], copy_only // f["node_bytes"]))
+
+
+def test_lds_plan_with_nothing_to_stage():
+    """No binary nodes: a forced treelet has nothing to stage and falls to mode 0. The host scene with no
+    primitives (flat and whole-scene copies of 0 bytes) is a flat list when nothing is forced, as every
+    scene of <= 24 primitives whose list fits; so is a one-leaf scene, whose device tree is its root."""
+    zero = {"flat": 0, "full": 0, "node_bytes": 128}
+    _plan_is(PB.lds_plan(None, forced_lm=2), zero, 0)
+    _plan_is(PB.lds_plan(None), zero, 3)
+    _plan_is(PB.lds_plan(None, forced_lm=1), zero, 1)
+    assert PB.lds_plan(None)["n_node4"] == 0
+    import _rayref as R
+    sc = R.scene("render1")
+    f = PB.lds_facts(sc)
+    assert f["nprim"] == 1
+    _plan_is(PB.lds_plan(sc, forced_lm=2), f, 0)
+    _plan_is(PB.lds_plan(sc), f, 3)
+    _plan_is(PB.lds_plan(sc, forced_lm=0), f, 0)
