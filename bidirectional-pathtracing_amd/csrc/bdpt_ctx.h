@@ -123,43 +123,9 @@ int render_blocks(Ctx* c, const int4* d_blocks, int nblocks, int spp_begin, int 
     }                                                                               \
   } while (0)
 
-// The scene as a kernel of LDS mode LM sees it (its tree width: lm_width(LM)).
+// The scene as a kernel of LDS mode LM sees it (scene_view, bdpt_scene.h) over the device copies.
 inline SceneView view_of(const Ctx* c, int LM) {
-  SceneView S;
-  const int W = lm_width(LM);
-  // the device copy of the very tree the kernels of this width traverse (hs.tree(W))
-  S.nodes = (const float4*)(&c->hs.tree(W) == &c->hs.bvh4 ? c->d_nodes4 : c->d_nodes2);
-  S.geom = (const float4*)c->d_geom;
-  S.shade = (const float4*)c->d_shade;
-  S.mats = c->d_mats;
-  S.lights = c->d_lights;
-  S.nlights = (int)c->hs.lights.size();
-  S.root = c->hs.tree(W).root;
-  S.lnodes = nullptr;
-  S.lgeom = nullptr;
-  S.lshade = nullptr;
-  S.lleaves = c->d_leaves;
-  S.nleaves = (int)c->hs.leaf_refs.size();
-  S.fn = flat_prims(c->hs, &S.fsph);
-  S.ntop = 0;
-  S.lstack = nullptr;
-  S.cam = c->hs.cam;
-  const HostScene& hs = c->hs;
-  S.env.light = hs.esc_light;
-  S.env.w = hs.env_w;
-  S.env.h = hs.env_h;
-  const size_t np = (size_t)hs.env_w * hs.env_h;
-  S.env.marg = c->d_env;
-  S.env.cond = c->d_env ? c->d_env + hs.env_h : nullptr;
-  S.env.pdf = c->d_env ? c->d_env + hs.env_h + np : nullptr;
-  S.env.rgb = c->d_env ? c->d_env + hs.env_h + 2 * np : nullptr;
-  S.env.gmarg = c->d_env ? (const int*)(c->d_env + hs.env_h + 5 * np) : nullptr;
-  S.env.gcond = S.env.gmarg ? S.env.gmarg + hs.env_gm + 1 : nullptr;
-  S.env.gm = hs.env_gm;
-  S.env.gc = hs.env_gc;
-  S.env.cx = hs.env_c[0]; S.env.cy = hs.env_c[1]; S.env.cz = hs.env_c[2];
-  S.env.rad = hs.env_rad;
-  return S;
+  return scene_view(c->hs, {c->d_nodes2, c->d_nodes4, c->d_geom, c->d_shade, c->d_mats, c->d_lights, c->d_leaves, c->d_env}, LM);
 }
 
 }  // namespace bdpt

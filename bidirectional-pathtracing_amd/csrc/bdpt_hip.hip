@@ -229,7 +229,7 @@ int bdpt_create(const bdpt_scene_desc* scene, const bdpt_params* params, void** 
   if (p.pipeline < 0 || p.pipeline > 2) { g_err = "bad pipeline (0 = auto, 1 = megakernel)"; return BDPT_E_INVALID; }
   Ctx* c = new Ctx();
   c->prm = p;
-  c->maxv = need <= 5 ? 5 : need <= 8 ? 8 : need <= 16 ? 16 : need <= 32 ? 32 : need <= 62 ? 62 : 126;
+  c->maxv = maxv_class(p.max_depth);
   // diagnostics / A-B switches, read once per ctx (tests set them before bdpt_create)
   auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
   c->env_lds_mode = env_int("BDPT_LDS_MODE", -1);

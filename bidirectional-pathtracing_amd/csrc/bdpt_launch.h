@@ -1,6 +1,6 @@
 // bdpt_launch.h — the host plumbing the C-ABI units share (bdpt_hip.hip, bdpt_denoise.hip,
 // bdpt_variance.hip, bdpt_adaptive.hip): the LDS budgets, a plan (bdpt_ldsplan.h) applied to a launch,
-// the persistent launch and its dispatch over the LDS modes, the tile -> block list, and the small
+// the persistent launch (dispatched over the LDS modes by bdpt_ldsplan.h dispatch_lm), the tile -> block list, and the small
 // helpers of an entry point (ticket word, lazy allocation, read-back, argument checks).
 #pragma once
 
@@ -8,7 +8,6 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <type_traits>
 #include <vector>
 
 #include "bdpt_ctx.h"
@@ -49,15 +48,6 @@ int launch_persistent(Ctx* c, K kernel, const char* name, size_t lds, const KP& 
   hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kBlock), lds, c->stream, kp);
   HIPCHK(hipGetLastError());
   return BDPT_OK;
-}
-
-// f(std::integral_constant<int, LM>) for the LDS mode lm: the kernels take it as a template argument.
-template <class F>
-int dispatch_lm(int lm, F&& f) {
-  if (lm == 3) return f(std::integral_constant<int, 3>{});
-  if (lm == 1) return f(std::integral_constant<int, 1>{});
-  if (lm == 2) return f(std::integral_constant<int, 2>{});
-  return f(std::integral_constant<int, 0>{});
 }
 
 // Tiles (raytrace_tile clips them to the frame, raytraced_renderer.cpp:600-604) -> 8x8 blocks

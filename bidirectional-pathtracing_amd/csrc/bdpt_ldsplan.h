@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <type_traits>
 
 #include "bdpt_scene.h"
 
@@ -41,6 +42,15 @@ inline LdsPlan lds_plan(const HostScene& hs, int forced_lm, size_t lds_max, size
   p.ntop = lm == 2 ? (int)std::min<size_t>((size_t)hs.tree(lm_width(2)).n_top, treelet_max / node_bytes(lm_width(2))) : 0;
   p.copy_bytes = lm == 3 ? p.flat_bytes : lm == 1 ? p.full_bytes : lm == 2 ? (size_t)p.ntop * node_bytes(lm_width(2)) : 0;
   return p;
+}
+
+// f(std::integral_constant<int, LM>) for the LDS mode lm: the kernels take it as a template argument.
+template <class F>
+int dispatch_lm(int lm, F&& f) {
+  if (lm == 3) return f(std::integral_constant<int, 3>{});
+  if (lm == 1) return f(std::integral_constant<int, 1>{});
+  if (lm == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 0>{});
 }
 
 }  // namespace bdpt

@@ -927,8 +927,20 @@ BDPT_HD int make_conn(const SceneView& S, const SampleParams& sp, const PA& P, R
   return CONN_RAY;
 }
 
+// sink.eye(x, y, v, direct) of a sink that has one: a sink that only takes the light image's splats
+// needs none and is not told.
+template <class Sink>
+BDPT_HD auto sink_eye(Sink& sink, int x, int y, f3 v, bool direct, int) -> decltype(sink.eye(x, y, v, direct), void()) {
+  sink.eye(x, y, v, direct);
+}
+template <class Sink>
+BDPT_HD void sink_eye(Sink&, int, int, f3, bool, long) {}
+
 // One pixel-sample, connections resolved in the reference's (i, j) order (host/test use; the
-// device kernel defers the connection rays to a wave-compacted queue instead).
+// device kernel defers the connection rays to a wave-compacted queue instead). The sink sees every
+// addend: splat(x, y, v) those of the light image, eye(x, y, v, direct), where it has that hook,
+// those of eye_sum, as they are added; direct: an s = 0 contribution (CONN_DIRECT), else a
+// connection ray that got through.
 template <int MAXV, int LM = 0, int EXT = 0, class Sink>
 BDPT_HD f3 render_sample(const SceneView& S, const SampleParams& sp, Paths<MAXV>& P, Counters& cnt,
                          int x, int y, uint32_t sample, Sink& sink) {
@@ -947,13 +959,18 @@ BDPT_HD f3 render_sample(const SceneView& S, const SampleParams& sp, Paths<MAXV>
       int kind = make_conn<EXT>(S, sp, PathsInRegs<MAXV, EXT>(P), g, i, j, cn);
       if (kind == CONN_DIRECT) {
         eye_sum = add(eye_sum, cn.val);
+        sink_eye(sink, x, y, cn.val, true, 0);
       } else if (kind == CONN_RAY) {
 #if defined(BDPT_STEP_HIST) && !defined(__HIP_DEVICE_COMPILE__)
         anyhit_tag() = i << 8 | j;
 #endif
         if (trace_any<LM>(S, cn.o, cn.d, BDPT_EPS_F, cn.tmax, cnt)) continue;
-        if (cn.splat >= 0) sink.splat(cn.splat % sp.W, cn.splat / sp.W, cn.val);
-        else eye_sum = add(eye_sum, cn.val);
+        if (cn.splat >= 0) {
+          sink.splat(cn.splat % sp.W, cn.splat / sp.W, cn.val);
+        } else {
+          eye_sum = add(eye_sum, cn.val);
+          sink_eye(sink, x, y, cn.val, false, 0);
+        }
       }
     }
   }

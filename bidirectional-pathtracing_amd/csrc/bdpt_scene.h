@@ -67,6 +67,13 @@ inline int kernel_flavour(const HostScene& hs, bool roulette, bool lens = false)
   return lens ? 3 : hs.inf_lights > 0 ? 2 : (hs.env_light >= 0 || roulette) ? 1 : 0;
 }
 
+// The depth class that renders max_depth (the MAXV template parameter: a subpath's fixed array),
+// or 0 past the deepest one (kMaxDepth).
+inline int maxv_class(int max_depth) {
+  const int need = max_depth < 1 ? 1 : max_depth;
+  return need <= 5 ? 5 : need <= 8 ? 8 : need <= 16 ? 16 : need <= 32 ? 32 : need <= 62 ? 62 : need <= 126 ? 126 : 0;
+}
+
 // bdpt_params.focal_distance as the kernels take it: 0 (or less) means 4.7, the PathTracer's rule.
 inline float lens_focal(double focal_distance) { return (float)(focal_distance > 0 ? focal_distance : 4.7); }
 
@@ -96,6 +103,57 @@ inline int flat_prims(const HostScene& hs, uint32_t* sph) {
     next += cnt;
   }
   return next;
+}
+
+// Where a HostScene's arrays lie for whoever traverses them: the scene's own vectors on the host,
+// their copies on the device.
+struct SceneArrays {
+  const float *nodes2, *nodes4;   // HostScene::bvh2 / bvh4
+  const float *geom, *shade;
+  const DMat* mats;
+  const DLight* lights;
+  const int32_t* leaves;          // HostScene::leaf_refs
+  const float* env;               // HostScene::env; null: no environment map
+};
+
+// The scene as a kernel of LDS mode LM sees it before anything is staged in LDS: the tree of that
+// mode's width (lm_width(LM)), no LDS copies, no treelet. The one place that knows HostScene::env's
+// layout.
+inline SceneView scene_view(const HostScene& hs, const SceneArrays& a, int LM) {
+  SceneView S;
+  const HostBvh& T = hs.tree(lm_width(LM));
+  S.nodes = (const float4*)(&T == &hs.bvh4 ? a.nodes4 : a.nodes2);
+  S.geom = (const float4*)a.geom;
+  S.shade = (const float4*)a.shade;
+  S.mats = a.mats;
+  S.lights = a.lights;
+  S.nlights = (int)hs.lights.size();
+  S.root = T.root;
+  S.lnodes = nullptr;
+  S.lgeom = nullptr;
+  S.lshade = nullptr;
+  S.lleaves = a.leaves;
+  S.nleaves = (int)hs.leaf_refs.size();
+  S.fn = flat_prims(hs, &S.fsph);
+  S.ntop = 0;
+  S.lstack = nullptr;
+  S.cam = hs.cam;
+  const float* e = hs.env.empty() ? nullptr : a.env;
+  const size_t h = (size_t)hs.env_h, np = (size_t)hs.env_w * h;
+  S.env.light = hs.esc_light;
+  S.env.w = hs.env_w;
+  S.env.h = hs.env_h;
+  S.env.marg = e;
+  S.env.cond = e ? e + h : nullptr;
+  S.env.pdf = e ? e + h + np : nullptr;
+  S.env.rgb = e ? e + h + 2 * np : nullptr;
+  S.env.gmarg = e ? (const int*)(e + h + 5 * np) : nullptr;
+  S.env.gcond = e ? S.env.gmarg + hs.env_gm + 1 : nullptr;
+  S.env.gm = hs.env_gm;
+  S.env.gc = hs.env_gc;
+  S.env.cx = hs.env_c[0]; S.env.cy = hs.env_c[1]; S.env.cz = hs.env_c[2];
+  S.env.rad = hs.env_rad;
+  return S;
 }
 
 // Returns BDPT_OK or an error code; err receives a message.

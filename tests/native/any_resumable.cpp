@@ -6,7 +6,7 @@
 
 template <int LM>
 static void resumable_check_lm(const HostScene& hs, const float* rays, int n, int* out) {
-  const SceneView S = trace_view<LM>(hs);
+  const SceneView S = host_view(hs, LM);
   for (int i = 0; i < n; i++) {
     const float* r = rays + 8 * (size_t)i;
     const f3 o = mk3(r[0], r[1], r[2]), d = mk3(r[3], r[4], r[5]);

@@ -5,9 +5,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "bdpt_core.h"
-#include "bdpt_ldsplan.h"
-#include "bdpt_scene.h"
+#include "core_cpu_host.h"
 
 using namespace bdpt;
 
@@ -26,159 +24,32 @@ struct AddendRec {
   }
 };
 
-// What core_cpu_render_rec records beside the frames (tests/_pixelbound.py): the light image's
-// splat count per pixel, and on request every splat, every eye-image addend (one connection's
-// value, before the 1 / spp factor) and every per-sample eye value (after it).
+// What core_cpu_render_rec records beside the frames and the splat counts (tests/_pixelbound.py),
+// each on request: every splat, every eye-image addend (one connection's value, before the 1 / spp
+// factor) and every per-sample eye value (after it).
 struct Recorder {
-  int* nsplat;   // W * H
   AddendRec splats, eye_addends, eye_samples;
 };
 
-struct HostSink {
-  std::vector<double>* light;
-  int W;
+struct RecSink : HostSink {
   Recorder* rec = nullptr;
   void splat(int x, int y, f3 v) {
-    size_t k = 3 * ((size_t)x + (size_t)y * W);
-    (*light)[k] += v.x; (*light)[k + 1] += v.y; (*light)[k + 2] += v.z;
-    if (rec) {
-      rec->nsplat[x + y * W]++;
-      rec->splats.put(x + y * W, v);
-    }
+    HostSink::splat(x, y, v);
+    rec->splats.put(x + y * W, v);
   }
+  void eye(int x, int y, f3 v, bool s0) {
+    HostSink::eye(x, y, v, s0);
+    rec->eye_addends.put(x + y * W, v);
+  }
+  void sample(int x, int y, f3 v) { rec->eye_samples.put(x + y * W, v); }
 };
 
-// render_sample (bdpt_paths.h), statement for statement, with every eye-image addend recorded
-// (tests/test_pixel_bounds.py holds the two bit-equal).
-template <int MAXV, int LM, int EXT>
-static f3 sample_recorded(const SceneView& S, const SampleParams& sp, Paths<MAXV>& P, Counters& cnt, int x, int y,
-                          uint32_t sample, HostSink& sink) {
-  Rng g;
-  prepare_sample<MAXV, LM, EXT>(S, sp, P, cnt, g, x, y, sample);
-  f3 eye_sum = splat3(0);
-  for (int i = 1; i < P.nE; i++) {
-    for (int j = 0; j < P.nL; j++) {
-      Conn cn;
-      int kind = make_conn<EXT>(S, sp, PathsInRegs<MAXV, EXT>(P), g, i, j, cn);
-      if (kind == CONN_DIRECT) {
-        eye_sum = add(eye_sum, cn.val);
-        sink.rec->eye_addends.put(x + y * sp.W, cn.val);
-      } else if (kind == CONN_RAY) {
-        if (trace_any<LM>(S, cn.o, cn.d, BDPT_EPS_F, cn.tmax, cnt)) continue;
-        if (cn.splat >= 0) sink.splat(cn.splat % sp.W, cn.splat / sp.W, cn.val);
-        else {
-          eye_sum = add(eye_sum, cn.val);
-          sink.rec->eye_addends.put(x + y * sp.W, cn.val);
-        }
-      }
-    }
-  }
-  return eye_sum;
-}
-
-template <int MAXV, int LM, bool EXT>
-static int run(const HostScene& hs, int W, int H, int spp, int M, uint64_t seed, int s0, int count,
-               const int* pixels, int npix, double* eye, double* light, double* stats, int rr,
-               Recorder* rec = nullptr) {
-  SceneView S;
-  const HostBvh& T = hs.tree(lm_width(LM));
-  S.nodes = (const float4*)T.nodes.data();
-  S.geom = (const float4*)hs.geom.data();
-  S.shade = (const float4*)hs.shade.data();
-  S.mats = hs.mats.data();
-  S.lights = hs.lights.data();
-  S.nlights = (int)hs.lights.size();
-  S.root = T.root;
-  // LM 1 reads the "LDS copy": on the CPU the same arrays (exercises the LDS-mode tree)
-  // LM 2 reads its BFS treelet [0, n_top) from the "LDS copy" (the same array on the CPU)
-  S.lnodes = LM == 1 || LM == 2 ? S.nodes : nullptr;
-  S.lgeom = LM == 1 || LM == 3 ? S.geom : nullptr;
-  S.lshade = LM == 3 ? S.shade : nullptr;
-  S.lleaves = hs.leaf_refs.data();
-  S.nleaves = (int)hs.leaf_refs.size();
-  S.fn = flat_prims(hs, &S.fsph);
-  S.ntop = LM == 2 ? T.n_top : 0;
-  S.lstack = nullptr;
-  S.cam = hs.cam;
-  const size_t np = (size_t)hs.env_w * hs.env_h;
-  S.env.light = hs.env_light;
-  S.env.w = hs.env_w;
-  S.env.h = hs.env_h;
-  S.env.marg = hs.env.data();
-  S.env.cond = hs.env.data() + hs.env_h;
-  S.env.pdf = hs.env.data() + hs.env_h + np;
-  S.env.rgb = hs.env.data() + hs.env_h + 2 * np;
-  S.env.gmarg = hs.env.empty() ? nullptr : (const int*)(hs.env.data() + hs.env_h + 5 * np);
-  S.env.gcond = hs.env.empty() ? nullptr : S.env.gmarg + hs.env_gm + 1;
-  S.env.gm = hs.env_gm;
-  S.env.gc = hs.env_gc;
-  S.env.cx = hs.env_c[0]; S.env.cy = hs.env_c[1]; S.env.cz = hs.env_c[2];
-  S.env.rad = hs.env_rad;
-  SampleParams sp;
-  sp.W = W; sp.H = H; sp.spp = spp; sp.max_depth = M; sp.seed = seed;
-  sp.rr = rr;
-  std::vector<double> lb((size_t)W * H * 3, 0.0);
-  HostSink sink{&lb, W, rec};
-  Counters cnt = {0, 0, 0, 0, 0, 0};
-  Paths<MAXV>* P = new Paths<MAXV>();
-  float inv = 1.0f / (float)spp;
-  int total = pixels ? npix : W * H;
-  for (int q = 0; q < total; q++) {
-    int x = pixels ? pixels[2 * q] : q % W, y = pixels ? pixels[2 * q + 1] : q / W;
-    for (int s = s0; s < s0 + count; s++) {
-      f3 v = rec ? sample_recorded<MAXV, LM, EXT>(S, sp, *P, cnt, x, y, (uint32_t)s, sink)
-                 : render_sample<MAXV, LM, EXT>(S, sp, *P, cnt, x, y, (uint32_t)s, sink);
-      size_t k = 3 * ((size_t)x + (size_t)y * W);
-      if (rec) rec->eye_samples.put(x + y * W, mk3(v.x * inv, v.y * inv, v.z * inv));
-      eye[k] += (double)(v.x * inv); eye[k + 1] += (double)(v.y * inv); eye[k + 2] += (double)(v.z * inv);
-    }
-  }
-  delete P;
-  for (size_t k = 0; k < lb.size(); k++) light[k] += lb[k];
-  if (stats) {
-    stats[0] = cnt.closest + cnt.shadow; stats[1] = cnt.closest; stats[2] = cnt.shadow;
-    stats[3] = cnt.nodes; stats[4] = cnt.tris; stats[5] = cnt.sphs; stats[6] = cnt.hits;
-  }
-  return 0;
-}
-
-template <int LM, bool EXT>
-static int render_maxv(const HostScene& hs, int W, int H, int spp, int M, uint64_t seed, int s0, int count,
-                       const int* pixels, int npix, double* eye, double* light, double* stats, int rr,
-                       Recorder* rec) {
-  int need = M < 1 ? 1 : M;
-  if (need <= 5) return run<5, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
-  if (need <= 8) return run<8, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
-  if (need <= 16) return run<16, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
-  if (need <= 32) return run<32, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
-  if (need <= 62) return run<62, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
-  if (need <= 126) return run<126, LM, EXT>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
-  return BDPT_E_UNSUPPORTED;
-}
-
-template <int LM>
-static int render_lm(const bdpt_scene_desc* d, int W, int H, int spp, int M, uint64_t seed, int s0,
-                     int count, const int* pixels, int npix, double* eye, double* light, double* stats, int rr,
-                     Recorder* rec = nullptr) {
-  HostScene hs;
-  std::string err;
-  int rc = build_host_scene(d, hs, err);
-  if (rc) { fprintf(stderr, "core_cpu: %s\n", err.c_str()); return rc; }
-  // the kernel selection of bdpt_create: EXT kernels for an environment light or roulette
-  if (hs.env_light >= 0 || rr)
-    return render_maxv<LM, true>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
-  return render_maxv<LM, false>(hs, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, rec);
-}
-
-// lds_mode 0: the HBM tree (lm_width(0) children per node); 1: the LDS-mode tree (lm_width(1));
-// 2: the HBM tree with its BFS treelet read through the LDS path (same array on the CPU); 3: flat list
+// lds_mode: host_render's (core_cpu_host.h). stats: 7 doubles, the first of host_render's. One thread.
 extern "C" int core_cpu_render(const bdpt_scene_desc* d, int W, int H, int spp, int M, uint64_t seed, int s0,
                                int count, const int* pixels, int npix, double* eye, double* light, double* stats,
                                int lds_mode, int rr) {
-  if (lds_mode == 1) return render_lm<1>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
-  if (lds_mode == 2) return render_lm<2>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
-  if (lds_mode == 3) return render_lm<3>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
-  return render_lm<0>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr);
+  const Job J = {W, H, spp, M, s0, count, rr, seed, pixels, npix, eye, light, stats, 7};
+  return host_render<1>("core_cpu", d, 0, lds_mode, J, HostSink());
 }
 
 // core_cpu_render with the addends on record (tests/_pixelbound.py; small frames): nsplat = W * H
@@ -192,13 +63,13 @@ extern "C" int core_cpu_render_rec(const bdpt_scene_desc* d, int W, int H, int s
                                    int lds_mode, int rr, int* nsplat, int* splat_pix, float* splat_rgb,
                                    int* addend_pix, float* addend_rgb, int* sample_pix, float* sample_rgb,
                                    const long long* cap, long long* n_out, float* vmin) {
-  Recorder rec = {nsplat, {splat_pix, splat_rgb, cap[0], 0, INFINITY}, {addend_pix, addend_rgb, cap[1], 0, INFINITY},
+  Recorder rec = {{splat_pix, splat_rgb, cap[0], 0, INFINITY}, {addend_pix, addend_rgb, cap[1], 0, INFINITY},
                   {sample_pix, sample_rgb, cap[2], 0, INFINITY}};
-  int rc;
-  if (lds_mode == 1) rc = render_lm<1>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, &rec);
-  else if (lds_mode == 2) rc = render_lm<2>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, &rec);
-  else if (lds_mode == 3) rc = render_lm<3>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, &rec);
-  else rc = render_lm<0>(d, W, H, spp, M, seed, s0, count, pixels, npix, eye, light, stats, rr, &rec);
+  RecSink sink;
+  sink.nsplat = nsplat;
+  sink.rec = &rec;
+  const Job J = {W, H, spp, M, s0, count, rr, seed, pixels, npix, eye, light, stats, 7};
+  const int rc = host_render<1>("core_cpu", d, 0, lds_mode, J, sink);
   n_out[0] = rec.splats.n; n_out[1] = rec.eye_addends.n; n_out[2] = rec.eye_samples.n;
   vmin[0] = rec.splats.vmin; vmin[1] = rec.eye_addends.vmin; vmin[2] = rec.eye_samples.vmin;
   return rc;
@@ -240,6 +111,30 @@ extern "C" int core_cpu_lds_plan(const bdpt_scene_desc* d, int infinite_lights, 
   return 0;
 }
 
+// host_view (core_cpu_host.h) of the description at lds_mode, that is scene_view (bdpt_scene.h) plus
+// the "LDS copies" (tests/test_scene_view.py). out19 = {the width of the tree S.nodes points into (2,
+// 4, 0: neither), root, ntop, nleaves, fn, env.light, the offsets in floats from HostScene::env of
+// env.marg, cond, pdf, rgb, gmarg, gcond (-1: null), whether lnodes, lgeom, lshade are set, and
+// to hold them against: lm_width(lds_mode), and from the HostScene itself the root of the tree of
+// that width, the n_top of LM 2's tree, its leaves}.
+extern "C" int core_cpu_view_facts(const bdpt_scene_desc* d, int infinite_lights, int lds_mode, int* out19) {
+  HostScene hs;
+  std::string err;
+  const int rc = build_host_scene(d, hs, err, false, infinite_lights != 0);
+  if (rc) return rc;
+  const SceneView S = host_view(hs, lds_mode);
+  out19[0] = (const float*)S.nodes == hs.bvh2.nodes.data() ? 2 : (const float*)S.nodes == hs.bvh4.nodes.data() ? 4 : 0;
+  out19[1] = S.root; out19[2] = S.ntop; out19[3] = S.nleaves; out19[4] = S.fn; out19[5] = S.env.light;
+  const void* env[6] = {S.env.marg, S.env.cond, S.env.pdf, S.env.rgb, S.env.gmarg, S.env.gcond};
+  for (int k = 0; k < 6; k++) out19[6 + k] = env[k] ? (int)((const float*)env[k] - hs.env.data()) : -1;
+  out19[12] = S.lnodes != nullptr; out19[13] = S.lgeom != nullptr; out19[14] = S.lshade != nullptr;
+  out19[15] = lm_width(lds_mode);
+  out19[16] = hs.tree(lm_width(lds_mode)).root;
+  out19[17] = hs.tree(lm_width(2)).n_top;
+  out19[18] = (int)hs.leaf_refs.size();
+  return 0;
+}
+
 extern "C" int core_cpu_scene_info(const bdpt_scene_desc* d, int* depth, int* ref_nodes, int* prim_ref) {
   HostScene hs;
   std::string err;
@@ -251,8 +146,6 @@ extern "C" int core_cpu_scene_info(const bdpt_scene_desc* d, int* depth, int* re
   return 0;
 }
 
-// The unidirectional PathTracer (bdpt_core.h pt_pixel) for the whole frame: image = W*H*3
-// (sampleBuffer), counts = W*H (sampleCountBuffer).
 // LDS mode 3's flat primitive run (flat_prims): its length, or 0 when the leaves are not one run
 extern "C" int core_cpu_flat_prims(const bdpt_scene_desc* d, uint32_t* sph_mask) {
   HostScene hs;
@@ -261,6 +154,8 @@ extern "C" int core_cpu_flat_prims(const bdpt_scene_desc* d, uint32_t* sph_mask)
   return flat_prims(hs, sph_mask);
 }
 
+// The unidirectional PathTracer (bdpt_core.h pt_pixel) for the whole frame: image = W*H*3
+// (sampleBuffer), counts = W*H (sampleCountBuffer).
 extern "C" int core_cpu_pt_render(const bdpt_scene_desc* d, int W, int H, int spp, int M, uint64_t seed,
                                   int ns_area_light, int batch, float tol, int hemisphere, double lens,
                                   double focal, double* image, int* counts) {
@@ -268,39 +163,7 @@ extern "C" int core_cpu_pt_render(const bdpt_scene_desc* d, int W, int H, int sp
   std::string err;
   int rc = build_host_scene(d, hs, err, true);
   if (rc) { fprintf(stderr, "core_cpu: %s\n", err.c_str()); return rc; }
-  SceneView S;
-  const HostBvh& T = hs.tree(lm_width(0));
-  S.nodes = (const float4*)T.nodes.data();
-  S.geom = (const float4*)hs.geom.data();
-  S.shade = (const float4*)hs.shade.data();
-  S.mats = hs.mats.data();
-  S.lights = hs.lights.data();
-  S.nlights = (int)hs.lights.size();
-  S.root = T.root;
-  S.lnodes = nullptr;
-  S.lgeom = nullptr;
-  S.lshade = nullptr;
-  S.lleaves = nullptr;
-  S.nleaves = 0;
-  S.fn = 0;
-  S.fsph = 0;
-  S.ntop = 0;
-  S.lstack = nullptr;
-  S.cam = hs.cam;
-  const size_t np = (size_t)hs.env_w * hs.env_h;
-  S.env.light = hs.env_light;
-  S.env.w = hs.env_w;
-  S.env.h = hs.env_h;
-  S.env.marg = hs.env.data();
-  S.env.cond = hs.env.data() + hs.env_h;
-  S.env.pdf = hs.env.data() + hs.env_h + np;
-  S.env.rgb = hs.env.data() + hs.env_h + 2 * np;
-  S.env.gmarg = hs.env.empty() ? nullptr : (const int*)(hs.env.data() + hs.env_h + 5 * np);
-  S.env.gcond = hs.env.empty() ? nullptr : S.env.gmarg + hs.env_gm + 1;
-  S.env.gm = hs.env_gm;
-  S.env.gc = hs.env_gc;
-  S.env.cx = hs.env_c[0]; S.env.cy = hs.env_c[1]; S.env.cz = hs.env_c[2];
-  S.env.rad = hs.env_rad;
+  const SceneView S = host_view(hs, 0);
   PtParams pp;
   pp.W = W; pp.H = H; pp.spp = spp; pp.max_depth = M; pp.seed = seed;
   pp.ns_area_light = ns_area_light; pp.batch = batch; pp.hemisphere = hemisphere; pp.tol = tol;
@@ -335,22 +198,8 @@ extern "C" int core_cpu_dev_tree(const bdpt_scene_desc* d, int* depth, int* node
 // component once gave an infinite inverse and NaN / -inf plane distances, bdpt_core.h safe_inv).
 // Returns the number of rays whose hit (primitive, t) differs; *hits = rays that hit something.
 template <int LM>
-static SceneView trace_view(const HostScene& hs) {
-  SceneView S = {};
-  const HostBvh& T = hs.tree(lm_width(LM));
-  S.nodes = (const float4*)T.nodes.data();
-  S.geom = (const float4*)hs.geom.data();
-  S.shade = (const float4*)hs.shade.data();
-  S.root = T.root;
-  S.lnodes = LM == 1 || LM == 2 ? S.nodes : nullptr;
-  S.lgeom = LM == 1 ? S.geom : nullptr;
-  S.ntop = LM == 2 ? T.n_top : 0;
-  return S;
-}
-
-template <int LM>
 static int trace_check_lm(const HostScene& hs, int n, uint64_t seed, int* hits) {
-  const SceneView S = trace_view<LM>(hs);
+  const SceneView S = host_view(hs, LM);
   const int np = (int)(hs.geom.size() / 12);
   float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f};
   for (int i = 0; i < np; i++) {
@@ -416,7 +265,7 @@ extern "C" int core_cpu_trace_check(const bdpt_scene_desc* d, int lds_mode, int 
 template <int LM>
 static void trace_rays_lm(const HostScene& hs, const float* rays, int n, int any_hit, float* out_t, int* out_prim,
                           unsigned* visits = nullptr) {
-  const SceneView S = trace_view<LM>(hs);
+  const SceneView S = host_view(hs, LM);
   for (int i = 0; i < n; i++) {
     Counters c = {};
     const float* r = rays + 8 * (size_t)i;

@@ -10,47 +10,11 @@
 #include "bdpt_atrous.h"
 #include "bdpt_features.h"
 #include "bdpt_scene.h"
+#include "core_cpu_host.h"
 
 using namespace bdpt;
 
 namespace {
-
-template <int LM>
-SceneView view_of_host(const HostScene& hs) {   // core_cpu_lens.cpp's
-  SceneView S;
-  const HostBvh& T = hs.tree(lm_width(LM));
-  S.nodes = (const float4*)T.nodes.data();
-  S.geom = (const float4*)hs.geom.data();
-  S.shade = (const float4*)hs.shade.data();
-  S.mats = hs.mats.data();
-  S.lights = hs.lights.data();
-  S.nlights = (int)hs.lights.size();
-  S.root = T.root;
-  S.lnodes = LM == 1 || LM == 2 ? S.nodes : nullptr;
-  S.lgeom = LM == 1 || LM == 3 ? S.geom : nullptr;
-  S.lshade = LM == 3 ? S.shade : nullptr;
-  S.lleaves = hs.leaf_refs.data();
-  S.nleaves = (int)hs.leaf_refs.size();
-  S.fn = flat_prims(hs, &S.fsph);
-  S.ntop = LM == 2 ? T.n_top : 0;
-  S.lstack = nullptr;
-  S.cam = hs.cam;
-  const size_t np = (size_t)hs.env_w * hs.env_h;
-  S.env.light = hs.esc_light;
-  S.env.w = hs.env_w;
-  S.env.h = hs.env_h;
-  S.env.marg = hs.env.data();
-  S.env.cond = hs.env.data() + hs.env_h;
-  S.env.pdf = hs.env.data() + hs.env_h + np;
-  S.env.rgb = hs.env.data() + hs.env_h + 2 * np;
-  S.env.gmarg = hs.env.empty() ? nullptr : (const int*)(hs.env.data() + hs.env_h + 5 * np);
-  S.env.gcond = hs.env.empty() ? nullptr : S.env.gmarg + hs.env_gm + 1;
-  S.env.gm = hs.env_gm;
-  S.env.gc = hs.env_gc;
-  S.env.cx = hs.env_c[0]; S.env.cy = hs.env_c[1]; S.env.cz = hs.env_c[2];
-  S.env.rad = hs.env_rad;
-  return S;
-}
 
 // The scene and FeatParams of a context of these settings, as bdpt_create / bdpt_render_features
 // set them up. integrator: 0 BDPT, 1 PathTracer.
@@ -81,7 +45,7 @@ int setup(const bdpt_scene_desc* d, int W, int H, int nsamp, uint64_t seed, int 
 
 template <int LM>
 void render_lm(const Setup& s, float* out8) {
-  const SceneView S = view_of_host<LM>(s.hs);
+  const SceneView S = host_view(s.hs, LM);
   Counters cnt = {0, 0, 0, 0, 0, 0};
   for (int y = 0; y < s.fp.H; y++)
     for (int x = 0; x < s.fp.W; x++) feature_pixel<LM>(S, s.fp, cnt, x, y, out8 + 8 * ((size_t)x + (size_t)y * s.fp.W));
@@ -89,7 +53,7 @@ void render_lm(const Setup& s, float* out8) {
 
 template <int LM>
 void samples_lm(const Setup& s, int n, const int* xys, int* prim, float* t, float* albedo, float* normal) {
-  const SceneView S = view_of_host<LM>(s.hs);
+  const SceneView S = host_view(s.hs, LM);
   Counters cnt = {0, 0, 0, 0, 0, 0};
   for (int k = 0; k < n; k++) {
     const FeatSample f = feature_sample<LM>(S, s.fp, cnt, xys[3 * k], xys[3 * k + 1], (uint32_t)xys[3 * k + 2]);
@@ -107,7 +71,7 @@ void put_ray(float* r, f3 o, f3 d, float tmin, float tmax) {
 // The first ray of BDPT's own eye walk: walk_begin (bdpt_paths.h) at flavour EXT.
 template <int EXT>
 void walk_begin_rays(const Setup& s, int n, const int* xys, float* rays) {
-  const SceneView S = view_of_host<0>(s.hs);
+  const SceneView S = host_view(s.hs, 0);
   SampleParams sp;
   sp.W = s.fp.W; sp.H = s.fp.H; sp.spp = s.fp.nsamp; sp.max_depth = 5; sp.seed = s.fp.seed;
   sp.rr = 0;
@@ -132,11 +96,7 @@ extern "C" int core_cpu_denoise_features(const bdpt_scene_desc* d, int W, int H,
   Setup s;
   const int rc = setup(d, W, H, nsamp, seed, integrator, lens_radius, focal_distance, infinite_lights, s);
   if (rc) return rc;
-  if (lds_mode == 1) render_lm<1>(s, out8);
-  else if (lds_mode == 2) render_lm<2>(s, out8);
-  else if (lds_mode == 3) render_lm<3>(s, out8);
-  else render_lm<0>(s, out8);
-  return 0;
+  return dispatch_lm(lds_mode, [&](auto LM) { render_lm<decltype(LM)::value>(s, out8); return 0; });
 }
 
 // The primary rays (n*8 floats: o, d, tmin, tmax) of the n samples xys = {x, y, s}.
@@ -161,11 +121,7 @@ extern "C" int core_cpu_denoise_sample_prims(const bdpt_scene_desc* d, int W, in
   Setup s;
   const int rc = setup(d, W, H, 1, seed, integrator, lens_radius, focal_distance, 0, s);
   if (rc) return rc;
-  if (lds_mode == 1) samples_lm<1>(s, n, xys, prim, t, albedo, normal);
-  else if (lds_mode == 2) samples_lm<2>(s, n, xys, prim, t, albedo, normal);
-  else if (lds_mode == 3) samples_lm<3>(s, n, xys, prim, t, albedo, normal);
-  else samples_lm<0>(s, n, xys, prim, t, albedo, normal);
-  return 0;
+  return dispatch_lm(lds_mode, [&](auto LM) { samples_lm<decltype(LM)::value>(s, n, xys, prim, t, albedo, normal); return 0; });
 }
 
 // The first ray of the BDPT eye walk of each sample, from walk_begin itself (the pinhole flavour,
@@ -187,7 +143,7 @@ extern "C" int core_cpu_denoise_pt_samples(const bdpt_scene_desc* d, int W, int 
   Setup s;
   const int rc = setup(d, W, H, 1, seed, 1, lens_radius, focal_distance, 0, s);
   if (rc) return rc;
-  const SceneView S = view_of_host<0>(s.hs);
+  const SceneView S = host_view(s.hs, 0);
   PtParams pp;
   pp.W = W; pp.H = H; pp.spp = 1; pp.max_depth = 1; pp.seed = seed;
   pp.ns_area_light = 1; pp.batch = 1; pp.hemisphere = 0; pp.tol = 0.0f;
